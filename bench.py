@@ -28,6 +28,12 @@ rank 0 prints the one JSON line with `n_gpus: N` and every rank's own step time 
                      SpyNet pair over gloo and runs the universal leg; the line says `"rehearsal": "cpu-port"` and its
                      metric is `cpu_port_rehearsal_steps_per_sec` -- never a result.
 
+    --dump-outputs DIR   after the timed steps, rank 0 writes what its last timed step computed as DIR/<name>.npy:
+                     the step's return value, the entries of PairAttack.result() that need no ground truth and the
+                     final / best perturbations and flows (--universal: the metrics and the two perturbations).  The
+                     inputs depend on the arguments only (seeded synthetic pair, seeded weights), so two builds can be
+                     compared output for output.
+
 The JSON line also carries
   roofline            the correlation-lookup forward kernel (the kernel BASELINE's north_star names): algorithmic
                       bytes/launch (SURVEY 8d: 20.44 MB at 55x128) / mean launch duration, against 8 TB/s HBM;
@@ -49,6 +55,7 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec
@@ -83,7 +90,13 @@ def parse():
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="host threads of the CPU baseline (0 = min(cores, 16): the 55x128-feature convolutions "
                          "stop scaling there; 64 threads measured 3x SLOWER than 16 on the 256-core box)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what rank 0's last timed step computed as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all; see dump_outputs).  bench_outputs/ is git-ignored")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -770,6 +783,62 @@ def cpu_baseline(net, h, w, nclosures, threads=0, boxconstraint="change_of_varia
 
 
 # --------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed in its last step, for comparing two builds output for output
+# --------------------------------------------------------------------------------------------------------------
+DUMP_BUDGET = 64 << 20     # bytes over all files, .npy headers included
+DUMP_SAMPLE_SEED = 1234
+
+
+# positions in PairAttack.result() that do not need a ground-truth flow (the synthetic pairs have none: aee_gt,
+# aee_gt_tgt and aee_adv_gt are None)
+RESULT_WITHOUT_GT = (1, 4, 5, 6, 7, 8, 9, 10, 11)
+
+
+def _scalars(values):
+    return np.array([float(v) for v in values], np.float64)
+
+
+def _host(x):
+    return x.detach().float().cpu().numpy()
+
+
+def pair_outputs(st, last):
+    """A PairAttack after its last timed step: the step's return value (aee_adv_tgt, aee_adv_pred, l2_delta12), the nine
+    entries of the reference's 12-tuple (`result()`) that need no ground truth, in tuple order, and the tensors `save()`
+    writes for the final and the best iterate, copied to the host at once (the re-prediction's outputs are graph buffers
+    that the next replay overwrites)."""
+    res = st.result()
+    out = {"step_return": _scalars(last), "result": _scalars(res[i] for i in RESULT_WITHOUT_GT)}
+    for name, x in (("delta1_final", st.delta1), ("delta2_final", st.delta2), ("flow_pred_final", st.flow_pred),
+                    ("delta1_best", st.delta1_min), ("delta2_best", st.delta2_min),
+                    ("flow_pred_best", st.flow_pred_min)):
+        out[name] = _host(x)
+    return out
+
+
+def universal_outputs(ua, last):
+    """A UniversalAttack after its last timed step: the step's metrics (in the order of its dict) and the perturbations."""
+    d1, d2 = ua.deltas()
+    return {"step_return": _scalars(last.values()), "delta1": _host(d1), "delta2": _host(d2)}
+
+
+def dump_outputs(directory, arrays):
+    """DIR/<name>.npy for every array.  If together they exceed DUMP_BUDGET, every array above 64 KB is replaced by a
+    fixed, seeded sample of its flattened elements (the same fraction of each, indices ascending), so that two runs of
+    the same arguments stay comparable element for element; the small ones (the metrics) are kept whole."""
+    os.makedirs(directory, exist_ok=True)
+    budget = DUMP_BUDGET - 256 * len(arrays)
+    small = sum(x.nbytes for x in arrays.values() if x.nbytes <= 1 << 16)
+    large = sum(x.nbytes for x in arrays.values() if x.nbytes > 1 << 16)
+    frac = min(1.0, (budget - small) / large) if large else 1.0
+    for name, x in sorted(arrays.items()):
+        if frac < 1.0 and x.nbytes > 1 << 16:
+            rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+            x = x.reshape(-1)[np.sort(rng.choice(x.size, int(x.size * frac), replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), x)
+
+
+# --------------------------------------------------------------------------------------------------------------
 def _sync():
     if torch.cuda.is_initialized():
         torch.cuda.synchronize()
@@ -816,9 +885,9 @@ def shared_forward_leg(net, h, w, dev, warmup, steps, sharding, model):
 
 
 def universal_leg(net, h, w, dev, rank, world, pairs_per_gpu, warmup, steps, sharding, cdev, model=None,
-                  use_graph=None):
+                  use_graph=None, dump=None):
     """K steps of UniversalAttack on one global batch of world*pairs_per_gpu pairs (rank r holds pairs
-    r*b .. r*b+b-1); returns the timing record (rank 0 fills the JSON from it)."""
+    r*b .. r*b+b-1); returns the timing record (rank 0 fills the JSON from it).  dump: --dump-outputs DIR."""
     seeds = [100 + rank * pairs_per_gpu + i for i in range(pairs_per_gpu)]
     t0 = time.perf_counter()
     ua = UniversalStepper(net, h, w, dev, seeds, use_graph=use_graph, model=model)
@@ -827,6 +896,8 @@ def universal_leg(net, h, w, dev, rank, world, pairs_per_gpu, warmup, steps, sha
         ua.step()
     col0 = ua.reducer.collectives if ua.reducer is not None else 0
     elapsed, closures, last = timed_steps(ua, steps, sharding)
+    if dump and rank == 0:
+        dump_outputs(dump, universal_outputs(ua, last))
     elapsed = sharding.max_scalar(elapsed, cdev)
     cols = (ua.reducer.collectives if ua.reducer is not None else 0) - col0
     flat = ua.reducer.flat.numel() * 4 if ua.reducer is not None else 0
@@ -987,6 +1058,8 @@ def rehearse_cpu(a, json_out):
         for _ in range(a.warmup):
             st.step()
         elapsed, closures, last = timed_steps(st, a.steps, sharding)
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, pair_outputs(st, last))
         per_rank = sharding.all_scalars(timed_steps.own_s, dev)
         elapsed = sharding.max_scalar(elapsed, dev)
         universal = None
@@ -1045,7 +1118,7 @@ def main():
 
     if a.universal:
         rec = universal_leg(a.net, h, w, dev, rank, world, a.pairs_per_gpu, a.warmup, a.steps, sharding, cdev,
-                            use_graph=use_graph)
+                            use_graph=use_graph, dump=a.dump_outputs)
         if rank == 0:
             out = {"metric": rec["metric"], "value": rec["value"], "unit": rec["unit"], "n_gpus": world,
                    "steps": a.steps, "warmup": a.warmup, "ms_per_step": rec["ms_per_step"],
@@ -1083,6 +1156,8 @@ def main():
         hip_ops.set_dispatch_timer(prof)
     elapsed, closures, last = timed_steps(st, a.steps, sharding)
     hip_ops.set_dispatch_timer(None)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, pair_outputs(st, last))
     per_rank = sharding.all_scalars(timed_steps.own_s, cdev)
     elapsed = sharding.max_scalar(elapsed, cdev)
     traced = None

@@ -17,6 +17,7 @@ What it does (SURVEY.md section 8c stub recipe):
 Fixtures:
   corr_block_*.npz        CorrBlock build + lookup, forward and backward   (models/raft/corr.py)
   spatial_corr_*.npz      spatial_correlation_sample forward/backward       (reference C++ sampler)
+  spatial_corr_refbuild.npz  the C++ build's raw forward/backward entry points, three parameter sets
   attack_math.npz         losses / extract_deltas / ScaledInputModel prologue
   losses_names.npz        avg_mse, f_mse, f_cosim, two_norm_avg_delta_squared, relu_penalty + gradients (losses.py)
   closure_<net>.npz       one PCFA closure: flow, loss, d loss / d nw_input  (128x160 or 128x192)
@@ -248,6 +249,29 @@ def golden_spatial_corr():
         save("spatial_corr_" + tag, in1=a, in2=b, params=params, out=out, grad_out=gout, gin1=a.grad, gin2=b.grad)
 
 
+# (kernel, patch, stride, padding, dilation, dilation_patch) of tests/test_oracle_cpu.py::SAMPLER_BUILD_CASES
+SAMPLER_BUILD_CASES = ((1, 9, 1, 0, 1, 1), (3, 5, 2, 2, 2, 2), (1, 21, 1, 0, 1, 2))
+
+
+def golden_spatial_corr_ref_build():
+    """The raw 12-integer forward / backward entry points of the reference's C++ build (oracle/_ref), case i with
+    params<i>, out<i>, gin1_<i>, gin2_<i> on one input pair; the output gradient of case i is tests.util.pattern(out
+    shape, i), computed by the test rather than stored."""
+    from oracle import build_ref
+    from tests.util import pattern
+    ref = build_ref.load_module()
+    g = torch.Generator().manual_seed(3)
+    a, b = torch.randn(2, 13, 9, 11, generator=g), torch.randn(2, 13, 9, 11, generator=g)
+    res = {"in1": a, "in2": b}
+    for i, (k, p, s, pad, dil, dp) in enumerate(SAMPLER_BUILD_CASES):
+        out = ref.forward(a, b, k, k, p, p, pad, pad, dil, dil, dp, dp, s, s)
+        go = torch.from_numpy(pattern(tuple(out.shape), i))
+        g1, g2 = ref.backward(a, b, go, k, k, p, p, pad, pad, dil, dil, dp, dp, s, s)
+        res.update({"params%d" % i: np.array([k, p, s, pad, dil, dp]), "out%d" % i: out,
+                    "gin1_%d" % i: g1, "gin2_%d" % i: g2})
+    save("spatial_corr_refbuild", **res)
+
+
 def golden_attack_math():
     import attack_PCFA
     from helper_functions import losses
@@ -472,11 +496,14 @@ def golden_universal():
 if __name__ == "__main__":
     install_stubs()
     torch.manual_seed(0)
-    which = sys.argv[1:] or ["corr", "scorr", "math", "losses", "closures", "trajectory", "flownet2", "universal"]
+    which = sys.argv[1:] or ["corr", "scorr", "scorr_build", "math", "losses", "closures", "trajectory", "flownet2",
+                             "universal"]
     if "corr" in which:
         golden_corr_block()
     if "scorr" in which:
         golden_spatial_corr()
+    if "scorr_build" in which:
+        golden_spatial_corr_ref_build()
     if "math" in which:
         golden_attack_math()
     if "losses" in which:

@@ -95,6 +95,57 @@ def test_bench_gpus1_does_not_spawn():
     assert out["n_gpus"] == 1 and "universal" not in out and len(out["per_rank_ms_per_step"]) == 1
 
 
+def test_bench_dump_outputs_are_the_last_timed_step_and_repeat(tmp_path):
+    """--dump-outputs DIR: what the last of exactly --steps timed steps computed, as float32 / float64 .npy files; the
+    inputs depend on the arguments only, so a second run writes the same arrays (the CPU port is deterministic)."""
+    import numpy as np
+    runs = []
+    for d in ("a", "b"):
+        env = _clean_env()
+        env["PCFA_BENCH_DETAIL"] = str(tmp_path / ("detail_%s.json" % d))
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup",
+                            "1", "--rehearse-cpu", "--dump-outputs", str(tmp_path / d)], env=env, capture_output=True,
+                           text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads(r.stdout.strip())
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        assert out["config"]["closure_evals_per_step"] == 10.0
+        files = sorted(os.listdir(str(tmp_path / d)))
+        runs.append((json.load(open(env["PCFA_BENCH_DETAIL"])), {f: np.load(str(tmp_path / d / f)) for f in files}))
+    (out, arrays), (_, again) = runs
+    assert set(arrays) == {"step_return.npy", "result.npy", "delta1_final.npy", "delta2_final.npy",
+                           "flow_pred_final.npy", "delta1_best.npy", "delta2_best.npy", "flow_pred_best.npy"}
+    assert all(x.dtype in (np.float32, np.float64) and np.isfinite(x).all() for x in arrays.values())
+    assert arrays["delta1_final.npy"].shape == (1, 3, 64, 64) and arrays["flow_pred_final.npy"].shape == (1, 2, 64, 64)
+    f = out["final"]
+    assert np.allclose(arrays["step_return.npy"], [f["aee_adv_tgt"], f["aee_adv_init"], f["l2_delta"]], rtol=1e-12)
+    assert arrays["result.npy"].shape == (9,) and arrays["result.npy"][1] == arrays["step_return.npy"][0]
+    assert float(np.abs(arrays["delta1_final.npy"]).max()) > 0
+    for name, x in arrays.items():
+        assert np.array_equal(x, again[name]), name
+
+
+def test_dump_outputs_samples_to_the_budget(tmp_path, monkeypatch):
+    """Over the byte budget every large array becomes the same seeded sample of its elements and the small ones stay
+    whole: the files fit, and two dumps of the same arrays are identical."""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 1 << 18)
+    rng = np.random.default_rng(0)
+    arrays = {"big": rng.standard_normal((3, 200, 200)).astype(np.float32),
+              "big2": rng.standard_normal((2, 100, 200)).astype(np.float64), "small": np.arange(5, dtype=np.float64)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    sizes = [os.path.getsize(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))]
+    assert len(sizes) == 3 and sum(sizes) <= 1 << 18
+    assert np.array_equal(np.load(str(tmp_path / "a" / "small.npy")), arrays["small"])
+    for name in ("big", "big2"):
+        x = np.load(str(tmp_path / "a" / (name + ".npy")))
+        assert x.dtype == arrays[name].dtype and 0 < x.size < arrays[name].size
+        assert np.all(np.isin(x, arrays[name]))
+        assert np.array_equal(x, np.load(str(tmp_path / "b" / (name + ".npy"))))
+
+
 def test_spawn_ranks_env_and_failure_propagation(tmp_path):
     from pcfa_amd import launch
     ok = tmp_path / "ok.py"

@@ -2093,7 +2093,8 @@ def test_bench_default_command_prints_one_short_strict_json_line(tmp_path):
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PCFA_BENCH_DETAIL=str(tmp_path / "detail.json"))
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--cpu-closures", "2"], env=env, capture_output=True, text=True, timeout=1500)
+                        "--cpu-closures", "2", "--dump-outputs", str(tmp_path / "outputs")], env=env, capture_output=True,
+                       text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -2113,6 +2114,15 @@ def test_bench_default_command_prints_one_short_strict_json_line(tmp_path):
     assert "error" not in out.get("pwcnet", {}) and "error" not in out.get("gma", {})
     detail = json.load(open(env["PCFA_BENCH_DETAIL"]))
     assert "kernel_families" in detail and "kernels" in detail and out["detail"] == bench.DETAIL_FILE
+    # --dump-outputs: the last timed step's outputs (not the extra eager steps after the timed region), under 64 MB
+    d = str(tmp_path / "outputs")
+    arrays = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+    assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64 << 20
+    assert all(x.dtype in (np.float32, np.float64) and np.isfinite(x).all() for x in arrays.values())
+    assert arrays["result"].shape == (9,) and arrays["result"][1] == arrays["step_return"][0]
+    assert arrays["delta1_final"].shape == (1, 3, 440, 1024) and arrays["flow_pred_final"].shape == (1, 2, 436, 1024)
+    f = detail["final"]
+    assert np.allclose(arrays["step_return"], [f["aee_adv_tgt"], f["aee_adv_init"], f["l2_delta"]], rtol=1e-12)
 
 
 @pytest.mark.parametrize("net,size", [("RAFT", (128, 160)), ("FlowNet2", (64, 128))])

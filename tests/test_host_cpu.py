@@ -241,9 +241,10 @@ def test_fgsm_step_and_driver():
     assert res["aee_predadv-tgt"] <= res["aee_pred-tgt"] + 1e-3      # two descent steps do not move away
 
 
-def test_universal_artifacts_round_trip_through_evaluate(tmp_path):
+def test_universal_artifacts_round_trip_through_evaluate(tmp_path, monkeypatch):
     """attack_l2_universal writes NNNNN_delta1_e{E}.npy; evaluate_PCFA reads them back, also across padding families."""
     from pcfa_amd import evaluate_PCFA
+    monkeypatch.setenv("PCFA_USE_CPU", "1")     # the CPU port, also where a GPU is visible (select_device)
     args = _cli(universal_perturbation=True, no_save=False, output_folder=str(tmp_path), steps=1, epochs=2)
     res = attack_PCFA.attack_l2_universal(args)
     run_dir = None

@@ -1,12 +1,13 @@
 """The oracle (CPU restatement) against the golden vectors produced by the REAL reference
-(tests/golden/make_golden.py) and against the reference's own C++ sampler build (oracle/_ref)."""
+(tests/golden/make_golden.py) and against the reference's own C++ sampler build (oracle/_ref, recorded under
+tests/golden/)."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from tests.util import load_golden, max_abs, rel_l2, t
+from tests.util import load_golden, max_abs, pattern, rel_l2, t
 
 
 @pytest.mark.parametrize("tag", ["a", "b"])
@@ -49,20 +50,29 @@ def test_spatial_corr_c_port_matches_reference(oracle_ops, tag):
     assert max_abs(b.grad, t(g["gin2"])) == 0.0
 
 
+# (kernel, patch, stride, padding, dilation, dilation_patch)
+SAMPLER_BUILD_CASES = ((1, 9, 1, 0, 1, 1), (3, 5, 2, 2, 2, 2), (1, 21, 1, 0, 1, 2))
+
+
 def test_spatial_corr_c_port_vs_reference_build(oracle_ops):
-    """Against the reference's own C++ build where it exists (oracle/_ref, built from /root/reference)."""
+    """Against the reference's own C++ build: its raw forward / backward entry points on three parameter sets, recorded
+    in tests/golden/spatial_corr_refbuild.npz (make_golden.py scorr_build).  Where the build exists (oracle/_ref), the
+    recorded vectors are first checked against it."""
     from oracle import build_ref
     ref = build_ref.load_module()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
-    gen = torch.Generator().manual_seed(3)
-    a, b = torch.randn(2, 13, 14, 19, generator=gen), torch.randn(2, 13, 14, 19, generator=gen)
-    for (k, p, s, pad, dil, dp) in ((1, 9, 1, 0, 1, 1), (3, 5, 2, 2, 2, 2), (1, 21, 1, 0, 1, 2)):
-        out_ref = ref.forward(a, b, k, k, p, p, pad, pad, dil, dil, dp, dp, s, s)
+    g = load_golden("spatial_corr_refbuild")
+    a, b = t(g["in1"]), t(g["in2"])
+    for i, (k, p, s, pad, dil, dp) in enumerate(SAMPLER_BUILD_CASES):
+        assert tuple(int(v) for v in g["params%d" % i]) == (k, p, s, pad, dil, dp)
+        out_ref, g1r, g2r = (t(g[n % i]) for n in ("out%d", "gin1_%d", "gin2_%d"))
+        go = t(pattern(tuple(out_ref.shape), i))     # the output gradient the build was recorded with
+        if ref is not None:
+            assert max_abs(ref.forward(a, b, k, k, p, p, pad, pad, dil, dil, dp, dp, s, s), out_ref) == 0.0
+            live1, live2 = ref.backward(a, b, go, k, k, p, p, pad, pad, dil, dil, dp, dp, s, s)
+            assert max_abs(live1, g1r) == 0.0 and max_abs(live2, g2r) == 0.0
         out = oracle_ops.spatial_correlation_sample(a, b, k, p, s, pad, dil, dp)
+        assert out.shape == out_ref.shape
         assert max_abs(out, out_ref) == 0.0
-        go = torch.randn(out.shape, generator=gen)
-        g1r, g2r = ref.backward(a, b, go, k, k, p, p, pad, pad, dil, dil, dp, dp, s, s)
         a2, b2 = a.clone().requires_grad_(True), b.clone().requires_grad_(True)
         oracle_ops.spatial_correlation_sample(a2, b2, k, p, s, pad, dil, dp).backward(go)
         assert max_abs(a2.grad, g1r) == 0.0 and max_abs(b2.grad, g2r) == 0.0

@@ -13,6 +13,14 @@ def load_golden(name):
     return {k: z[k] for k in z.files}
 
 
+def pattern(shape, salt):
+    """Deterministic pseudo-random float32 array, exact on every host (integer hash -> multiples of 1/512 in [-2, 2)):
+    a gradient that a fixture does not need to store."""
+    i = np.arange(int(np.prod(shape)), dtype=np.uint64) + np.uint64(salt) * np.uint64(1000003)
+    h = (i * np.uint64(2654435761)) % np.uint64(4294967291)
+    return (((h % np.uint64(2048)).astype(np.float32) - 1024) / 512).reshape(shape)
+
+
 def t(a, device="cpu"):
     """numpy -> float32 torch tensor"""
     return torch.from_numpy(np.ascontiguousarray(a)).float().to(device)
