@@ -590,6 +590,32 @@ PCFA_API int pcfa_pwc_warp_bwd_det(const float* x, const float* flo, const float
                           float* grad_flo, void* workspace, size_t workspace_bytes, int B, int C, int H, int W,
                           float mask_threshold, float flow_scale, void* stream);
 
+/* SpyNet's backward warp (models/SpyNet/SpyNet.py:86-102): grid = clamp(hor[x] + flo_x * sx, -1, 1) (y likewise with ver,
+ * sy), out = grid_sample(x, grid) (bilinear, zero padding, align_corners = False, no mask).  hor: [W], ver: [H] -- the
+ * reference's linspace(-1, 1, .) vectors, taken as given; sx = 1 / ((W - 1) / 2), sy = 1 / ((H - 1) / 2) rounded to fp32.
+ * The backward is the fixed-point scatter of pcfa_pwc_warp_bwd_det for grad_x and a gather for grad_flo through the
+ * clamp's mask (gradient where -1 <= grid <= 1): bit-reproducible.  workspace >= pcfa_spynet_warp_bwd_workspace_bytes(),
+ * 8-B aligned.  {clear + max, scatter, finish} */
+PCFA_API int pcfa_spynet_warp_fwd(const float* x, const float* flo, const float* hor, const float* ver, float* out, int B,
+                                  int C, int H, int W, float sx, float sy, void* stream);
+PCFA_API size_t pcfa_spynet_warp_bwd_workspace_bytes(int B, int C, int H, int W);
+PCFA_API int pcfa_spynet_warp_bwd(const float* x, const float* flo, const float* hor, const float* ver,
+                                  const float* grad_out, float* grad_x, float* grad_flo, void* workspace,
+                                  size_t workspace_bytes, int B, int C, int H, int W, float sx, float sy, void* stream);
+
+/* 7x7 / stride 1 / pad 3 convolution on the fp32 matrix cores for frozen weights (SpyNet's Basic, SpyNet.py:56-84):
+ *   out = act(conv(x') + bias) + addend,   x' = x where mask > 0, else 0 (mask NULL: x' = x)
+ * x / mask: [B][Cin][H][W], out / addend: [B][Cout][H][W], bias: [Cout] or NULL, act: relu != 0.  The data gradient is the
+ * same call on grad_out with mask = the layer's saved output and the weight w.transpose(0, 1).flip(2, 3).  `packed` (16-B
+ * aligned, pcfa_conv7x7_packed_floats floats) holds the weight [Cout][Cin][7][7] in MFMA operand order: with
+ * (mt, cot) = pcfa_conv7x7_tile(Cout), Cout padded to cot, Cin to 4 (zeros), the order is
+ * [Cout / cot][Cin / 4][cot / mt][4 / (64 / mt)][7][7][64 / mt][mt] (packed on the host, ops.spynet.conv7x7_pack).
+ * Fixed summation order, no atomics, no scratch: bitwise reproducible. */
+PCFA_API int pcfa_conv7x7_tile(int Cout, int* mt, int* cot);
+PCFA_API long long pcfa_conv7x7_packed_floats(int Cin, int Cout);
+PCFA_API int pcfa_conv7x7(const float* x, const float* mask, const float* packed, const float* bias, const float* addend,
+                          float* out, int B, int Cin, int Cout, int H, int W, int relu, void* stream);
+
 /* 3x3 / stride 1 / pad 1 convolution with N <= 4 output channels and its data gradient (frozen weights): the
  * flow-prediction layers -- FlowHead.conv2 of RAFT / GMA (models/raft/update.py:6-14), predict_flow of PWC-Net
  * (models/PWCNet/PWCNet.py:37-38) and FlowNet2 (models/FlowNet/submodules.py:33-34).  A stream over the input

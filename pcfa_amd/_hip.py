@@ -154,6 +154,13 @@ SIGNATURES = {
     "pcfa_deconv4s2_fewout_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "pcfa_deconv4s2_fewout_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "pcfa_deconv4s2_fewout_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "pcfa_spynet_warp_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_float, _P]),
+    "pcfa_spynet_warp_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "pcfa_spynet_warp_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_size_t, c_int, c_int, c_int, c_int, c_float, c_float,
+                                     _P]),
+    "pcfa_conv7x7_tile": (c_int, [c_int, POINTER(c_int), POINTER(c_int)]),
+    "pcfa_conv7x7_packed_floats": (c_longlong, [c_int, c_int]),
+    "pcfa_conv7x7": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "pcfa_upsample_bilinear_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
     "pcfa_upsample_bilinear_bwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
     "pcfa_instnorm_workspace_bytes": (c_size_t, [c_int, c_longlong]),

@@ -493,13 +493,19 @@ class PairsInFlight:
         process is captured by ONE host thread, i.e. with one rocBLAS handle, and a handle owns ONE device workspace that
         all its launches share in stream order -- replayed side by side, two lanes' products use it at the same time.
         Observed (r05, tools/dev/flight_scaling.py GMA 436x1024, two lanes): the first step never returns.  The package's own
-        products take their split-K scratch from the caller, so the build with gma_gemm = "hip" is safe in flight."""
+        products take their split-K scratch from the caller, so the build with gma_gemm = "hip" is safe in flight; likewise
+        SpyNet with spynet_ops = "hip" (own 7x7 convolutions and warp, no scratch shared between lanes)."""
         net = getattr(getattr(attack, "args", None), "net", None)
-        if net in ("SpyNet", "FlowNet2"):
-            # their closures keep library convolutions (SpyNet's 7x7 layers, FlowNet2's transposed convolutions): the same
-            # question, never validated -- refused rather than left to chance
-            raise ValueError("%s keeps library convolutions inside its captured closure: several pairs in flight are "
-                             "validated for RAFT, PWCNet and GMA (gma_gemm='hip') only" % net)
+        if net == "FlowNet2":
+            # its closure keeps library convolutions (the transposed convolutions): the same question, never validated --
+            # refused rather than left to chance
+            raise ValueError("FlowNet2 keeps library convolutions inside its captured closure: several pairs in flight are "
+                             "validated for RAFT, PWCNet, GMA (gma_gemm='hip') and SpyNet (spynet_ops='hip') only")
+        if net == "SpyNet" and config.cfg(attack.model).spynet_ops != "hip":
+            # the default build runs Basic's 7x7 layers on MIOpen; the spynet_ops = "hip" build holds no library kernel
+            raise ValueError("SpyNet with Config.spynet_ops='lib' keeps library convolutions inside its captured closure and "
+                             "cannot run several pairs in flight: build the model with spynet_ops='hip' "
+                             "(PCFA_SPYNET_OPS=hip) or use --pairs_in_flight 1")
         if net == "GMA" and config.cfg(attack.model).gma_gemm != "hip":
             raise ValueError("GMA with Config.gma_gemm='lib' cannot run several pairs in flight (the lanes' captured rocBLAS "
                              "products would share one handle's workspace): build the model with gma_gemm='hip' "

@@ -38,6 +38,10 @@ class Config:
     warp_bwd_deterministic: bool = True  # fixed-point scatter in the warp backward (False: hardware fp32 atomics)
     pwc_fold_glue: bool = True           # RGB->BGR in conv1a's weights, `up_flow * s` inside the warp, decoder inputs written
                                          # straight into the dense-block buffer, one re-gridding copy between dilated layers
+    # ---- SpyNet (nets/spynet.py) ----
+    spynet_ops: str = "lib"              # Basic's 7x7 layers, the warp and the flow up-sampling: "lib" (MIOpen, grid_sample,
+                                         # interpolate) | "hip" (ops.conv7x7, ops.spynet_warp, ops.upsample_bilinear: no library
+                                         # kernel, no atomic-accumulating backward -- reproducible, allowed in flight)
     # ---- attack loop (attack_PCFA.py) ----
     reuse_pair_graphs: bool = True       # pairs of one shape share static buffers + hipGraphs
     max_cached_shapes: int = 4           # graph sets kept per model (LRU); KITTI under /8 padding has three padded shapes
@@ -49,6 +53,7 @@ class Config:
                    defer_relu=_env_bool("PCFA_DEFER_RELU", True),
                    gma_gemm=os.environ.get("PCFA_GMA_GEMM", "lib"),
                    conv1x1=os.environ.get("PCFA_CONV1X1", "lib"),
+                   spynet_ops=os.environ.get("PCFA_SPYNET_OPS", "lib"),
                    max_cached_shapes=int(os.environ.get("PCFA_MAX_CACHED_SHAPES", "4")))
 
     def __post_init__(self):
@@ -56,6 +61,8 @@ class Config:
             raise ValueError("Config.gma_gemm must be 'lib' or 'hip', got %r" % (self.gma_gemm,))
         if self.conv1x1 not in ("lib", "hip"):
             raise ValueError("Config.conv1x1 must be 'lib' or 'hip', got %r" % (self.conv1x1,))
+        if self.spynet_ops not in ("lib", "hip"):
+            raise ValueError("Config.spynet_ops must be 'lib' or 'hip', got %r" % (self.spynet_ops,))
         if self.max_cached_shapes < 1:
             raise ValueError("Config.max_cached_shapes must be >= 1")
 

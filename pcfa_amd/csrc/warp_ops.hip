@@ -67,17 +67,57 @@ __device__ __forceinline__ WarpTaps warp_taps(float ix, float iy, int H, int W) 
   return t;
 }
 
+// SpyNet's coordinate mode (reference models/SpyNet/SpyNet.py:86-102, nets/spynet.py backward_warp):
+//   grid = clamp(linspace(-1, 1, W)[x] + flow_x * sx, -1, 1)   (sx = 1 / ((W - 1) / 2) rounded to fp32: ATen's GPU division
+//   by a scalar multiplies by the reciprocal), the same along y; then grid_sample (bilinear, zeros, align_corners = False).
+// The linspace vectors are inputs (not re-derived); each step is rounded on its own, as the separate library launches are.
+struct SpyGrid {
+  const float* hor;   // [W] linspace(-1, 1, W)
+  const float* ver;   // [H] linspace(-1, 1, H)
+  float sx, sy;
+};
+
+// clamp(g, -1, 1) with NaN passed through (torch.clamp); *ok: the clamp passes the gradient (-1 <= g <= 1)
+__device__ __forceinline__ float spy_grid(float base, float flow, float scale, bool* ok) {
+#pragma clang fp contract(off)
+  const float g = base + flow * scale;
+  *ok = g >= -1.f && g <= 1.f;
+  return g != g ? g : fminf(fmaxf(g, -1.f), 1.f);
+}
+
+__device__ __forceinline__ float spy_unnormalize(float g, int size) {   // ((g + 1) * size - 1) / 2, the fma of warp_coord
+#pragma clang fp contract(off)
+  return fmaf(g + 1.f, (float)size, -1.f) / 2.f;
+}
+
+// sample position of pixel p: PWC-Net (SPY = false: meshgrid + fs * flo, normalised by W - 1) or SpyNet (SPY = true)
+template <bool SPY>
+__device__ __forceinline__ void sample_pos(const float* __restrict__ fb, long long p, long long plane, int px, int py, int H,
+                                           int W, float fs, const SpyGrid& sg, float& ix, float& iy, bool& okx, bool& oky) {
+  if constexpr (SPY) {
+    ix = spy_unnormalize(spy_grid(sg.hor[px], fb[p], sg.sx, &okx), W);
+    iy = spy_unnormalize(spy_grid(sg.ver[py], fb[plane + p], sg.sy, &oky), H);
+  } else {
+    ix = warp_coord((float)px, mul_rounded(fb[p], fs), W);
+    iy = warp_coord((float)py, mul_rounded(fb[plane + p], fs), H);
+    okx = oky = true;
+  }
+}
+
 // grid = (pixel blocks, channel groups, B); thread = one pixel, channels c = group, group + G, ...
+template <bool SPY>
 __global__ __launch_bounds__(256) void pwc_warp_fwd_kernel(const float* __restrict__ x, const float* __restrict__ flo,
                                                           float* __restrict__ out, int C, int H, int W,
-                                                          float mask_thresh, float fs) {
+                                                          float mask_thresh, float fs, SpyGrid sg) {
   const long long plane = (long long)H * W;
   const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= plane) return;
   const int b = blockIdx.z, G = gridDim.y;
   const int py = (int)(p / W), px = (int)(p % W);
   const float* fb = flo + (size_t)b * 2 * plane;
-  const float ix = warp_coord((float)px, mul_rounded(fb[p], fs), W), iy = warp_coord((float)py, mul_rounded(fb[plane + p], fs), H);
+  float ix, iy;
+  bool okx, oky;
+  sample_pos<SPY>(fb, p, plane, px, py, H, W, fs, sg, ix, iy, okx, oky);
   const WarpTaps t = warp_taps(ix, iy, H, W);
   // weights as grid_sampler_2d forms them: nw = (ix_se - ix) * (iy_se - iy), ...
   const float ex = (float)(t.x0 + 1) - ix, ey = (float)(t.y0 + 1) - iy;  // ix_se - ix, iy_se - iy
@@ -110,13 +150,17 @@ __global__ __launch_bounds__(256) void pwc_warp_bwd_kernel(const float* __restri
                                                           const float* __restrict__ gout, float* __restrict__ gx,
                                                           float* __restrict__ gflo, int C, int H, int W,
                                                           float mask_thresh, float fs) {
+  constexpr bool SPY = false;
+  const SpyGrid sg{};
   const long long plane = (long long)H * W;
   const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= plane) return;
   const int b = blockIdx.z, G = gridDim.y;
   const int py = (int)(p / W), px = (int)(p % W);
   const float* fb = flo + (size_t)b * 2 * plane;
-  const float ix = warp_coord((float)px, mul_rounded(fb[p], fs), W), iy = warp_coord((float)py, mul_rounded(fb[plane + p], fs), H);
+  float ix, iy;
+  bool okx, oky;
+  sample_pos<SPY>(fb, p, plane, px, py, H, W, fs, sg, ix, iy, okx, oky);
   const WarpTaps t = warp_taps(ix, iy, H, W);
   const float ex = (float)(t.x0 + 1) - ix, ey = (float)(t.y0 + 1) - iy;
   const float nw = ex * ey, ne = t.wx1 * ey, sw = ex * t.wy1, se = t.wx1 * t.wy1;
@@ -213,11 +257,21 @@ __device__ __forceinline__ void fix_add(long long* p, float v, double scale) {
   atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double2ll_rn((double)v * scale));
 }
 
+// a channel group's share of d loss / d (scaled flow) before the finish multiplies by the scale:
+// PWC-Net: d ix / d grid = W / 2, d grid / d flo = 2 / max(W - 1, 1) (the reference divides, then doubles);
+// SpyNet: d ix / d grid = W / 2 (grid_sampler's gix_mult), then the clamp's mask (every group applies it: sum of zeros)
+template <bool SPY>
+__device__ __forceinline__ float flow_grad(float gi, int size, bool ok) {
+  if constexpr (SPY) return ok ? 0.5f * (float)size * gi : 0.f;
+  else return 2.0f * ((0.5f * (float)size * gi) / (float)max(size - 1, 1));
+}
+
+template <bool SPY>
 __global__ __launch_bounds__(256) void pwc_warp_bwd_det_kernel(const float* __restrict__ x, const float* __restrict__ flo,
                                                               const float* __restrict__ gout, long long* __restrict__ gxi,
                                                               float* __restrict__ gfpart, const float* __restrict__ bmax,
                                                               int nblk, int C, int H, int W, float mask_thresh,
-                                                              float fs) {
+                                                              float fs, SpyGrid sg) {
   __shared__ float red[4];
   const double scale = ldexp(1.0, warp_fix_shift(bmax, nblk, red));
   const long long plane = (long long)H * W;
@@ -227,7 +281,9 @@ __global__ __launch_bounds__(256) void pwc_warp_bwd_det_kernel(const float* __re
   const int py = (int)(p / W), px = (int)(p % W);
   const float* fb = flo + (size_t)b * 2 * plane;
   float* gf = gfpart + ((size_t)blockIdx.y * B + b) * 2 * plane;   // this channel group's partial flow gradient
-  const float ix = warp_coord((float)px, mul_rounded(fb[p], fs), W), iy = warp_coord((float)py, mul_rounded(fb[plane + p], fs), H);
+  float ix, iy;
+  bool okx, oky;
+  sample_pos<SPY>(fb, p, plane, px, py, H, W, fs, sg, ix, iy, okx, oky);
   const WarpTaps t = warp_taps(ix, iy, H, W);
   const float ex = (float)(t.x0 + 1) - ix, ey = (float)(t.y0 + 1) - iy;
   const float nw = ex * ey, ne = t.wx1 * ey, sw = ex * t.wy1, se = t.wx1 * t.wy1;
@@ -274,8 +330,8 @@ __global__ __launch_bounds__(256) void pwc_warp_bwd_det_kernel(const float* __re
       giy = tap_fma(giy, vse, t.wx1, g, false);
     }
   }
-  gf[p] = 2.0f * ((0.5f * (float)W * gix) / (float)max(W - 1, 1));
-  gf[plane + p] = 2.0f * ((0.5f * (float)H * giy) / (float)max(H - 1, 1));
+  gf[p] = flow_grad<SPY>(gix, W, okx);
+  gf[plane + p] = flow_grad<SPY>(giy, H, oky);
 }
 
 // The same scatter through an LDS window.  The cost of the kernel above is its global atomics, and an atomic instruction
@@ -286,10 +342,11 @@ __global__ __launch_bounds__(256) void pwc_warp_bwd_det_kernel(const float* __re
 // on consecutive texels of a row (2 cache lines per 32 lanes).  Taps outside the window (a flow that tears the tile
 // apart) go to global memory directly, as above.
 constexpr int WT = 16, WWIN = 32, WCH = 4;
+template <bool SPY>
 __global__ __launch_bounds__(256) void pwc_warp_bwd_det_lds_kernel(
     const float* __restrict__ x, const float* __restrict__ flo, const float* __restrict__ gout, long long* __restrict__ gxi,
     float* __restrict__ gfpart, const float* __restrict__ bmax, int nblk, int C, int H, int W, float mask_thresh, float fs,
-    int tiles_x) {
+    int tiles_x, SpyGrid sg) {
   __shared__ float red[4];
   __shared__ unsigned long long win[WCH][WWIN * WWIN];
   __shared__ int s_org[2];
@@ -304,7 +361,9 @@ __global__ __launch_bounds__(256) void pwc_warp_bwd_det_lds_kernel(
   const int b = blockIdx.z, G = gridDim.y, B = gridDim.z;
   const float* fb = flo + (size_t)b * 2 * plane;
   float* gf = gfpart + ((size_t)blockIdx.y * B + b) * 2 * plane;
-  const float ix = warp_coord((float)px, mul_rounded(fb[p], fs), W), iy = warp_coord((float)py, mul_rounded(fb[plane + p], fs), H);
+  float ix, iy;
+  bool okx, oky;
+  sample_pos<SPY>(fb, p, plane, px, py, H, W, fs, sg, ix, iy, okx, oky);
   const WarpTaps t = warp_taps(ix, iy, H, W);
   const float ex = (float)(t.x0 + 1) - ix, ey = (float)(t.y0 + 1) - iy;
   const float nw = ex * ey, ne = t.wx1 * ey, sw = ex * t.wy1, se = t.wx1 * t.wy1;
@@ -384,8 +443,8 @@ __global__ __launch_bounds__(256) void pwc_warp_bwd_det_lds_kernel(
     __syncthreads();
   }
   if (inside) {
-    gf[p] = act ? 2.0f * ((0.5f * (float)W * gix) / (float)max(W - 1, 1)) : 0.f;
-    gf[plane + p] = act ? 2.0f * ((0.5f * (float)H * giy) / (float)max(H - 1, 1)) : 0.f;
+    gf[p] = act ? flow_grad<SPY>(gix, W, okx) : 0.f;
+    gf[plane + p] = act ? flow_grad<SPY>(giy, H, oky) : 0.f;
   }
 }
 
@@ -393,7 +452,8 @@ __global__ __launch_bounds__(256) void pwc_warp_finish_kernel(const long long* _
                                                               const float* __restrict__ gfpart,
                                                               const float* __restrict__ bmax, int nblk,
                                                               float* __restrict__ gx, float* __restrict__ gflo,
-                                                              long long nx, long long nf, int G, float fs) {
+                                                              long long nx, long long nf, int G, float fs,
+                                                              float fsy, long long plane) {
   __shared__ float red[4];
   const int shift = warp_fix_shift(bmax, nblk, red);
   const long long step = (long long)gridDim.x * blockDim.x;
@@ -411,7 +471,8 @@ __global__ __launch_bounds__(256) void pwc_warp_finish_kernel(const long long* _
       const long long j = i - nx;
       float s = gfpart[j];
       for (int g = 1; g < G; ++g) s += gfpart[j + (long long)g * nf];   // channel groups in index order
-      gflo[j] = mul_rounded(s, fs);   // gradient of the scaled flow times the scale, as autograd's mul backward
+      gflo[j] = mul_rounded(s, (j / plane) & 1 ? fsy : fs);   // gradient of the scaled flow times the scale (per axis), as
+                                                               // autograd's mul backward
     }
   }
 }
@@ -445,34 +506,31 @@ int channel_groups(long long plane, int C) {
   return g;
 }
 
-}  // namespace
-
-extern "C" int pcfa_pwc_warp_fwd(const float* x, const float* flo, float* out, int B, int C, int H, int W,
-                                 float mask_threshold, float flow_scale, void* stream) {
-  if (!x || !flo || !out || B < 1 || C < 1 || H < 1 || W < 1) return PCFA_ERR_INVALID_ARG;
+template <bool SPY>
+int warp_fwd(const float* x, const float* flo, float* out, int B, int C, int H, int W, float mask_threshold, float flow_scale,
+             SpyGrid sg, hipStream_t s) {
   const long long plane = (long long)H * W;
   dim3 grid(pcfa_cdiv(plane, 256), channel_groups(plane, C), B);
-  pcfa_launch(pwc_warp_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, flo, out, C, H, W, mask_threshold, flow_scale);
+  pcfa_launch(pwc_warp_fwd_kernel<SPY>, grid, dim3(256), 0, s, x, flo, out, C, H, W, mask_threshold, flow_scale, sg);
   PCFA_LAUNCH_CHECK();
   return PCFA_OK;
 }
 
-extern "C" size_t pcfa_pwc_warp_bwd_det_workspace_bytes(int B, int C, int H, int W) {
+size_t warp_bwd_det_workspace_bytes(int B, int C, int H, int W) {
   if (B < 1 || C < 1 || H < 1 || W < 1) return 0;
   const long long plane = (long long)H * W;
   return (size_t)B * C * plane * sizeof(long long) + (size_t)channel_groups(plane, C) * B * 2 * plane * sizeof(float) +
          WARP_BMAX * sizeof(float);
 }
 
-extern "C" int pcfa_pwc_warp_bwd_det(const float* x, const float* flo, const float* grad_out, float* grad_x,
-                                     float* grad_flo, void* workspace, size_t workspace_bytes, int B, int C, int H,
-                                     int W, float mask_threshold, float flow_scale, void* stream) {
-  if (!x || !flo || !grad_out || !grad_x || !grad_flo || !workspace || B < 1 || C < 1 || H < 1 || W < 1)
-    return PCFA_ERR_INVALID_ARG;
-  if (workspace_bytes < pcfa_pwc_warp_bwd_det_workspace_bytes(B, C, H, W)) return PCFA_ERR_WORKSPACE;
+// {clear + max, fixed-point scatter + flow-gradient partials, finish}; flow_scale / fsy: the finish's factor along x / y
+template <bool SPY>
+int warp_bwd_det(const float* x, const float* flo, const float* grad_out, float* grad_x, float* grad_flo, void* workspace,
+                 size_t workspace_bytes, int B, int C, int H, int W, float mask_threshold, float flow_scale, float fsy,
+                 SpyGrid sg, hipStream_t s) {
+  if (workspace_bytes < warp_bwd_det_workspace_bytes(B, C, H, W)) return PCFA_ERR_WORKSPACE;
   if (reinterpret_cast<uintptr_t>(workspace) & 7) return PCFA_ERR_INVALID_ARG;
   const long long plane = (long long)H * W;
-  hipStream_t s = (hipStream_t)stream;
   const long long nx = (long long)B * C * plane, nf = (long long)B * 2 * plane;
   const int G = channel_groups(plane, C);
   long long* gxi = (long long*)workspace;
@@ -486,18 +544,61 @@ extern "C" int pcfa_pwc_warp_bwd_det(const float* x, const float* flo, const flo
   if (lds_window && plane >= 256) {   // (tiny planes: the window's clear / flush passes cost more than they save)
     const int tiles_x = pcfa_cdiv(W, WT), tiles_y = pcfa_cdiv(H, WT);
     dim3 grid((unsigned)(tiles_x * tiles_y), G, B);
-    pcfa_launch(pwc_warp_bwd_det_lds_kernel, grid, dim3(256), 0, s, x, flo, grad_out, gxi, gfpart, (const float*)bmax, nblk,
-                C, H, W, mask_threshold, flow_scale, tiles_x);
+    pcfa_launch(pwc_warp_bwd_det_lds_kernel<SPY>, grid, dim3(256), 0, s, x, flo, grad_out, gxi, gfpart, (const float*)bmax,
+                nblk, C, H, W, mask_threshold, flow_scale, tiles_x, sg);
   } else {
     dim3 grid(pcfa_cdiv(plane, 256), G, B);
-    pcfa_launch(pwc_warp_bwd_det_kernel, grid, dim3(256), 0, s, x, flo, grad_out, gxi, gfpart, (const float*)bmax, nblk, C,
-                H, W, mask_threshold, flow_scale);
+    pcfa_launch(pwc_warp_bwd_det_kernel<SPY>, grid, dim3(256), 0, s, x, flo, grad_out, gxi, gfpart, (const float*)bmax, nblk,
+                C, H, W, mask_threshold, flow_scale, sg);
   }
   PCFA_LAUNCH_CHECK();
   pcfa_launch(pwc_warp_finish_kernel, dim3((int)min((nx + nf + 255) / 256, 4096LL)), dim3(256), 0, s,
-              (const long long*)gxi, (const float*)gfpart, (const float*)bmax, nblk, grad_x, grad_flo, nx, nf, G, flow_scale);
+              (const long long*)gxi, (const float*)gfpart, (const float*)bmax, nblk, grad_x, grad_flo, nx, nf, G, flow_scale,
+              fsy, plane);
   PCFA_LAUNCH_CHECK();
   return PCFA_OK;
+}
+
+}  // namespace
+
+extern "C" int pcfa_pwc_warp_fwd(const float* x, const float* flo, float* out, int B, int C, int H, int W,
+                                 float mask_threshold, float flow_scale, void* stream) {
+  if (!x || !flo || !out || B < 1 || C < 1 || H < 1 || W < 1) return PCFA_ERR_INVALID_ARG;
+  return warp_fwd<false>(x, flo, out, B, C, H, W, mask_threshold, flow_scale, SpyGrid{}, (hipStream_t)stream);
+}
+
+extern "C" size_t pcfa_pwc_warp_bwd_det_workspace_bytes(int B, int C, int H, int W) {
+  return warp_bwd_det_workspace_bytes(B, C, H, W);
+}
+
+extern "C" int pcfa_pwc_warp_bwd_det(const float* x, const float* flo, const float* grad_out, float* grad_x,
+                                     float* grad_flo, void* workspace, size_t workspace_bytes, int B, int C, int H,
+                                     int W, float mask_threshold, float flow_scale, void* stream) {
+  if (!x || !flo || !grad_out || !grad_x || !grad_flo || !workspace || B < 1 || C < 1 || H < 1 || W < 1)
+    return PCFA_ERR_INVALID_ARG;
+  return warp_bwd_det<false>(x, flo, grad_out, grad_x, grad_flo, workspace, workspace_bytes, B, C, H, W, mask_threshold,
+                             flow_scale, flow_scale, SpyGrid{}, (hipStream_t)stream);
+}
+
+extern "C" int pcfa_spynet_warp_fwd(const float* x, const float* flo, const float* hor, const float* ver, float* out, int B,
+                                    int C, int H, int W, float sx, float sy, void* stream) {
+  if (!x || !flo || !hor || !ver || !out || B < 1 || C < 1 || H < 1 || W < 1) return PCFA_ERR_INVALID_ARG;
+  return warp_fwd<true>(x, flo, out, B, C, H, W, -1.f, 1.f, SpyGrid{hor, ver, sx, sy}, (hipStream_t)stream);
+}
+
+extern "C" size_t pcfa_spynet_warp_bwd_workspace_bytes(int B, int C, int H, int W) {
+  return warp_bwd_det_workspace_bytes(B, C, H, W);
+}
+
+extern "C" int pcfa_spynet_warp_bwd(const float* x, const float* flo, const float* hor, const float* ver,
+                                    const float* grad_out, float* grad_x, float* grad_flo, void* workspace,
+                                    size_t workspace_bytes, int B, int C, int H, int W, float sx, float sy, void* stream) {
+  if (!x || !flo || !hor || !ver || !grad_out || !grad_x || !grad_flo || !workspace || B < 1 || C < 1 || H < 1 || W < 1)
+    return PCFA_ERR_INVALID_ARG;
+  // mask threshold -1: no validity mask (every pixel passes); the finish multiplies the flow gradient by sx / sy (the
+  // kernels form the SpyNet grid from sg, not from the flow_scale argument)
+  return warp_bwd_det<true>(x, flo, grad_out, grad_x, grad_flo, workspace, workspace_bytes, B, C, H, W, -1.f, sx, sy,
+                            SpyGrid{hor, ver, sx, sy}, (hipStream_t)stream);
 }
 
 extern "C" int pcfa_pwc_warp_bwd(const float* x, const float* flo, const float* grad_out, float* grad_x,

@@ -9,6 +9,10 @@ configuration of BASELINE.json (config 0).
 Unlike the reference, constructing the network does not read 60 weight files
 from disk; `load_pretrained(dir)` does that on request with the reference's file
 naming (SpyNet.py:75-81).
+
+Config.spynet_ops = "hip" (opt-in) runs Basic's 7x7 layers on ops.conv7x7, the warp on ops.spynet_warp and the flow
+up-sampling on ops.upsample_bilinear: a closure then holds no library kernel and no atomic-accumulating backward.  The
+modules and the state dict are the same in both builds.
 """
 import math
 import os
@@ -16,6 +20,9 @@ import os
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from .. import ops
+from ..config import cfg
 
 
 class Preprocess(nn.Module):
@@ -50,8 +57,16 @@ class Basic(nn.Module):
             nn.Conv2d(32, 16, kernel_size=7, stride=1, padding=3), nn.ReLU(inplace=False),
             nn.Conv2d(16, 2, kernel_size=7, stride=1, padding=3))
 
-    def forward(self, x):
-        return self.moduleBasic(x)
+    def forward(self, x, addend=None):
+        """moduleBasic(x) [+ addend] (the caller's `+ up`, SpyNet.py:153)."""
+        if cfg(self).spynet_ops == "hip" and x.is_cuda:
+            o = ops.get()
+            convs = [self.moduleBasic[i] for i in range(0, 10, 2)]
+            for conv in convs[:-1]:
+                x = o.conv7x7(x, conv.weight, conv.bias, relu=True)
+            return o.conv7x7(x, convs[-1].weight, convs[-1].bias, addend=addend)
+        y = self.moduleBasic(x)
+        return y if addend is None else y + addend
 
 
 def backward_warp(feat, flow):
@@ -101,12 +116,24 @@ class Network(nn.Module):
         flow = torch.zeros(firsts[0].size(0), 2, int(math.floor(firsts[0].size(2) / 2.0)),
                            int(math.floor(firsts[0].size(3) / 2.0)), device=first.device, dtype=first.dtype)
         all_flows = [None] * self.nlevels
+        hip = cfg(self).spynet_ops == "hip" and first.is_cuda
         for lvl in range(len(firsts)):
-            up = F.interpolate(flow, scale_factor=2, mode='bilinear', align_corners=False) * 2.0
-            if up.size(2) != firsts[lvl].size(2):
-                up = F.pad(up, [0, 0, 0, 1], 'replicate')
-            if up.size(3) != firsts[lvl].size(3):
-                up = F.pad(up, [0, 1, 0, 0], 'replicate')
-            flow = self.moduleBasic[lvl](torch.cat([firsts[lvl], backward_warp(seconds[lvl], up), up], 1)) + up
+            if hip:
+                # `interpolate(...) * 2.0` with a gather backward (the product by 2 is exact: the same values)
+                up = ops.get().upsample_bilinear(flow, 2, 2.0)
+                if tuple(up.shape[2:]) != tuple(firsts[lvl].shape[2:]):
+                    # the replicate pad below (and its atomic backward) never runs for /64-padded inputs
+                    raise ValueError("SpyNet with spynet_ops='hip' needs image sides divisible by 2**(nlevels-1) "
+                                     "(level %d: flow %s vs image %s)" % (lvl, tuple(up.shape[2:]),
+                                                                          tuple(firsts[lvl].shape[2:])))
+                warped = ops.get().spynet_warp(seconds[lvl], up)
+                flow = self.moduleBasic[lvl](torch.cat([firsts[lvl], warped, up], 1), addend=up)
+            else:
+                up = F.interpolate(flow, scale_factor=2, mode='bilinear', align_corners=False) * 2.0
+                if up.size(2) != firsts[lvl].size(2):
+                    up = F.pad(up, [0, 0, 0, 1], 'replicate')
+                if up.size(3) != firsts[lvl].size(3):
+                    up = F.pad(up, [0, 1, 0, 0], 'replicate')
+                flow = self.moduleBasic[lvl](torch.cat([firsts[lvl], backward_warp(seconds[lvl], up), up], 1)) + up
             all_flows[self.nlevels - lvl - 1] = flow
         return all_flows if self.training else flow

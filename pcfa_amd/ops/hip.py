@@ -14,6 +14,7 @@ Operator boundaries mirrored (reference file:line) -- one module per group:
   gru          gru_step, gru_gates(_packed), gru_update, bias_relu, fanout, flow_step, convex_upsample
                                                               models/raft/update.py:33-60, raft.py:72-83,122-137
   gma          attention_softmax, attn_times_value, gemm_f32  models/gma/gma.py:34-77,79-115
+  spynet       conv7x7, spynet_warp                        models/SpyNet/SpyNet.py:56-102 (Config.spynet_ops = "hip")
   attack_math  box_transform, extract_deltas(_joint), loss_delta_constraint, avg_epe, two_norm_*, pm1_pair
                                                               helper_functions/own_models.py:62-85, attack_PCFA.py:20-37, losses.py
 """
@@ -33,3 +34,4 @@ from .gru import *  # noqa: F401,F403
 from .profiling import *  # noqa: F401,F403
 from .pwc import *  # noqa: F401,F403
 from .pwc import _PwcCostVolume  # noqa: F401
+from .spynet import *  # noqa: F401,F403
