@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """PCFA attack-steps/sec on MI355X (BASELINE.json metric; workload = configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one `--steps` iteration of pcfa_attack on one synthetic 436x1024 image pair with RAFT
@@ -11,12 +11,19 @@ One "step" = one `--steps` iteration of pcfa_attack on one synthetic 436x1024 im
 not a restatement.  Inputs are resident in HBM before the timed region.  Every rank attacks its own pair
 (disjoint perturbations, no data-path collective): weak scaling, value = N*K / max-over-ranks time.
 
+A plain run does only what the headline figure needs: set-up, `--warmup` steps, the `--steps` timed steps, the
+`--dump-outputs` files and the JSON line.
+
+    --full        everything else as well, after the timed steps: the per-kernel and roofline rows, the CPU baseline
+                  and its parity record, calibration, the set-up of later pairs and the extra legs (PWC-Net, GMA, pairs
+                  in flight, shared forward; `--no-*-leg` / `--no-cpu-baseline` skip single ones).  With N > 1 it also
+                  appends a short universal leg after the timed region (`"universal": {...}` in the JSON line) so that
+                  a multi-GPU run exercises the all-reduce path too.
+
     --universal   BASELINE config 5 instead: ONE perturbation pair shared by all images, data parallel over the
                   batch (`--pairs-per-gpu` pairs on every rank), one RCCL all-reduce of [grad delta1 | grad delta2 |
                   loss] per closure (`pcfa_amd.attack_PCFA.UniversalAttack.step`).  value = pair-steps/s =
                   N * pairs-per-gpu * K / time (weak scaling: per-GPU work fixed).
-With N > 1 the default (per-pair) run also appends a short universal leg after the timed region
-(`"universal": {...}` in the JSON line) so that a multi-GPU run exercises the all-reduce path too.
 
 Started WITHOUT torchrun (`python bench.py --gpus N`, no RANK/WORLD_SIZE in the environment) the process becomes a
 launcher: before anything touches the GPU it starts N fresh rank processes of this script (pcfa_amd.launch.spawn_ranks:
@@ -34,7 +41,7 @@ rank 0 prints the one JSON line with `n_gpus: N` and every rank's own step time 
                      inputs depend on the arguments only (seeded synthetic pair, seeded weights), so two builds can be
                      compared output for output.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline            the correlation-lookup forward kernel (the kernel BASELINE's north_star names): algorithmic
                       bytes/launch (SURVEY 8d: 20.44 MB at 55x128) / mean launch duration, against 8 TB/s HBM;
   kernels             the other hand-written kernels of the path with their own roofline rows (RAFT/GMA: pyramid GEMMs,
@@ -70,9 +77,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--net", default="RAFT", choices=["RAFT", "GMA", "PWCNet", "SpyNet", "FlowNet2"])
     ap.add_argument("--size", default="436x1024")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beside the headline figure "
+                         "(kernel and roofline rows, CPU baseline + parity, calibration, the extra legs)")
     ap.add_argument("--universal", action="store_true", help="time the universal attack (config 5) instead")
     ap.add_argument("--pairs-per-gpu", type=int, default=1, help="--universal: local batch size")
-    ap.add_argument("--no-universal-leg", action="store_true", help="N > 1: skip the short universal leg")
+    ap.add_argument("--no-universal-leg", action="store_true", help="--full, N > 1: skip the short universal leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--rehearse-cpu", action="store_true",
                     help="no GPU: rehearse launcher + collectives with the CPU port on a tiny workload (not a result)")
@@ -1141,7 +1151,7 @@ def main():
     setup_eager = time.perf_counter() - t0
     from pcfa_amd import hip_ops
     corr_net = a.net in ("RAFT", "GMA")
-    gpu_parity = parity_closure(st) if (rank == 0 and world == 1 and not a.no_cpu_baseline) else None
+    gpu_parity = parity_closure(st) if (a.full and rank == 0 and world == 1 and not a.no_cpu_baseline) else None
     # HIP events attached to every dispatch of the named kernel (on the stream it is launched on)
     prof = hip_ops.DispatchTimer() if corr_net else None
     t0 = time.perf_counter()
@@ -1160,6 +1170,71 @@ def main():
         dump_outputs(a.dump_outputs, pair_outputs(st, last))
     per_rank = sharding.all_scalars(timed_steps.own_s, cdev)
     elapsed = sharding.max_scalar(elapsed, cdev)
+    out = None
+    if rank == 0:
+        hp, wp = st.image1.shape[-2:]
+        out = {
+            "metric": "attack_steps_per_sec", "value": world * a.steps / elapsed, "unit": "attack_steps/s",
+            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / a.steps,
+            "per_rank_ms_per_step": [1e3 * t / a.steps for t in per_rank],
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": "%s, 1 synthetic %dx%d pair per GPU (padded %dx%d), disjoint delta, "
+                                   "change_of_variables, delta_bound=0.005, zero target, L-BFGS max_iter=10"
+                                   % (a.net, h, w, hp, wp), "weights": "random:1234",
+                       "closure_evals_per_step": closures / a.steps, "parallelism": "pairs sharded 1/GPU",
+                       "closure_launch": "hipGraph replay" if graph_active else
+                                         ("eager (hipGraph capture FAILED: see the log)" if use_graph else "eager"),
+                       "timed_object": "pcfa_amd.attack_PCFA.PairAttack.step (the body of pcfa_attack's loop)"},
+            "closure_evals_per_sec": world * closures / elapsed,
+            "per_pair_setup_s": {"upload_init_forward_target": setup_eager, "graph_warmup_and_capture": setup_graph,
+                                 "note": "first pair of a shape: paid once, outside the timed steps; later pairs of "
+                                         "the same shape reuse buffers + graphs (--full: second_pair_same_shape)"},
+            "final": {"aee_adv_tgt": last[0], "aee_adv_init": last[1], "l2_delta": last[2]},
+        }
+    if a.full:
+        full_legs(a, out, st, dev, rank, world, use_graph, prof, gpu_parity, sharding)
+    if world > 1 and a.full and not a.no_universal_leg:
+        # last, and under a deadline: see ExtraLegGuard
+        def publish(record):
+            if rank == 0:
+                out["universal"] = record
+                emit(out, json_out)
+
+        guard = ExtraLegGuard(float(os.environ.get("PCFA_BENCH_EXTRA_LEG_DEADLINE_S", "240")), publish)
+        try:
+            universal = universal_leg(a.net, h, w, dev, rank, world, 1, 1, 2, sharding, cdev, model=st.model,
+                                      use_graph=use_graph)
+        except Exception as e:  # noqa: BLE001 -- the headline line must survive a failure of the extra leg
+            universal = {"error": repr(e)}
+        guard.publish(universal)
+        # leave together: a rank that left alone (its leg raised) would make the launcher end the others before the
+        # deadline lets rank 0 print.  The store is the rendezvous' own TCP store, not a collective.
+        try:
+            from datetime import timedelta
+            store = torch.distributed.distributed_c10d._get_default_store()
+            store.set("pcfa_bench_leg_%d" % rank, "error" if "error" in universal else "ok")
+            store.wait(["pcfa_bench_leg_%d" % r for r in range(world)], timedelta(seconds=guard.seconds + 60.0))
+            sharding.shutdown()
+        except Exception as e:  # noqa: BLE001 -- the line is out; the guard ends this rank at the deadline
+            print("rank %d: leaving through the deadline: %r" % (rank, e), file=sys.stderr)
+            time.sleep(guard.seconds + 60.0)
+        guard.cancel()
+        return out
+    if rank == 0:
+        emit(out, json_out)
+    sharding.shutdown()
+    return out
+
+
+def full_legs(a, out, st, dev, rank, world, use_graph, prof, gpu_parity, sharding):
+    """--full: everything beside the headline figure, after its timed steps, on the pair `st` they stepped (`out`: the
+    headline record on rank 0, None elsewhere).  Every rank runs the extra steps; rank 0 adds the graph-replay kernel
+    trace, the roofline / kernel / family / optimiser rows, the set-up of later pairs, calibration, the un-fused lookup at
+    batch 2 and the pairs-in-flight, shared-forward, CPU-baseline, PWC-Net and GMA legs to `out`."""
+    from pcfa_amd import hip_ops
+    h, w = (int(v) for v in a.size.lower().split("x"))
+    corr_net = a.net in ("RAFT", "GMA")
     traced = None
     # PCFA_BENCH_NO_TRACER=1: skip the in-process tracer (set when an external profiler already owns it)
     if use_graph and rank == 0 and os.environ.get("PCFA_BENCH_NO_TRACER", "0") != "1" and \
@@ -1214,29 +1289,9 @@ def main():
         except Exception as e:  # noqa: BLE001 -- informational
             second_pair = {"error": repr(e)}
 
-    out = None
     if rank == 0:
         hp, wp = st.image1.shape[-2:]
-        out = {
-            "metric": "attack_steps_per_sec", "value": world * a.steps / elapsed, "unit": "attack_steps/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / a.steps,
-            "per_rank_ms_per_step": [1e3 * t / a.steps for t in per_rank],
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": "%s, 1 synthetic %dx%d pair per GPU (padded %dx%d), disjoint delta, "
-                                   "change_of_variables, delta_bound=0.005, zero target, L-BFGS max_iter=10"
-                                   % (a.net, h, w, hp, wp), "weights": "random:1234",
-                       "closure_evals_per_step": closures / a.steps, "parallelism": "pairs sharded 1/GPU",
-                       "closure_launch": "hipGraph replay" if graph_active else
-                                         ("eager (hipGraph capture FAILED: see the log)" if use_graph else "eager"),
-                       "timed_object": "pcfa_amd.attack_PCFA.PairAttack.step (the body of pcfa_attack's loop)"},
-            "closure_evals_per_sec": world * closures / elapsed,
-            "per_pair_setup_s": {"upload_init_forward_target": setup_eager, "graph_warmup_and_capture": setup_graph,
-                                 "second_pair_same_shape": second_pair,
-                                 "note": "first pair of a shape: paid once, outside the timed steps; later pairs of "
-                                         "the same shape reuse buffers + graphs (second_pair_same_shape)"},
-            "final": {"aee_adv_tgt": last[0], "aee_adv_init": last[1], "l2_delta": last[2]},
-        }
+        out["per_pair_setup_s"]["second_pair_same_shape"] = second_pair
         lb = lbfgs_record(traced, st, lbfgs_history)
         if lb is not None:
             out["lbfgs"] = lb
@@ -1337,37 +1392,6 @@ def main():
                 out["gma"] = gma_leg(a, dev, sharding)
             except Exception as e:  # noqa: BLE001
                 out["gma"] = {"error": repr(e)}
-    if world > 1 and not a.no_universal_leg:
-        # last, and under a deadline: see ExtraLegGuard
-        def publish(record):
-            if rank == 0:
-                out["universal"] = record
-                emit(out, json_out)
-
-        guard = ExtraLegGuard(float(os.environ.get("PCFA_BENCH_EXTRA_LEG_DEADLINE_S", "240")), publish)
-        try:
-            universal = universal_leg(a.net, h, w, dev, rank, world, 1, 1, 2, sharding, cdev, model=st.model,
-                                      use_graph=use_graph)
-        except Exception as e:  # noqa: BLE001 -- the headline line must survive a failure of the extra leg
-            universal = {"error": repr(e)}
-        guard.publish(universal)
-        # leave together: a rank that left alone (its leg raised) would make the launcher end the others before the
-        # deadline lets rank 0 print.  The store is the rendezvous' own TCP store, not a collective.
-        try:
-            from datetime import timedelta
-            store = torch.distributed.distributed_c10d._get_default_store()
-            store.set("pcfa_bench_leg_%d" % rank, "error" if "error" in universal else "ok")
-            store.wait(["pcfa_bench_leg_%d" % r for r in range(world)], timedelta(seconds=guard.seconds + 60.0))
-            sharding.shutdown()
-        except Exception as e:  # noqa: BLE001 -- the line is out; the guard ends this rank at the deadline
-            print("rank %d: leaving through the deadline: %r" % (rank, e), file=sys.stderr)
-            time.sleep(guard.seconds + 60.0)
-        guard.cancel()
-        return out
-    if rank == 0:
-        emit(out, json_out)
-    sharding.shutdown()
-    return out
 
 
 if __name__ == "__main__":

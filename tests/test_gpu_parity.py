@@ -1762,8 +1762,9 @@ def test_rccl_single_rank_collectives_run_on_gpu(tmp_path):
 
 def test_bench_gpus2_spawns_two_ranks_on_one_gpu():
     """`python bench.py --gpus 2` with no torchrun environment (the driver's command shape) must start two rank
-    processes.  On this one-GPU box the ranks share the device and use gloo (PCFA_BENCH_SHARE_GPU / _BACKEND exist for
-    exactly this rehearsal); on an 8-GPU node the same launcher gives every rank its own GPU and RCCL."""
+    processes; with --full the job also runs the universal leg.  On this one-GPU box the ranks share the device and use
+    gloo (PCFA_BENCH_SHARE_GPU / _BACKEND exist for exactly this rehearsal); on an 8-GPU node the same launcher gives
+    every rank its own GPU and RCCL."""
     import json
     import os
     import subprocess
@@ -1772,7 +1773,7 @@ def test_bench_gpus2_spawns_two_ranks_on_one_gpu():
     env = _rank_env()
     env.update(PCFA_BENCH_BACKEND="gloo", PCFA_BENCH_SHARE_GPU="1")
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-                        "--size", "128x160"], env=env, capture_output=True, text=True, timeout=900)
+                        "--size", "128x160", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout
@@ -1797,7 +1798,7 @@ def test_bench_gpus2_headline_survives_an_extra_leg_that_does_not_return():
     env = _rank_env()
     env.update(PCFA_BENCH_BACKEND="gloo", PCFA_BENCH_SHARE_GPU="1", PCFA_BENCH_EXTRA_LEG_DEADLINE_S="0")
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-                        "--size", "128x160"], env=env, capture_output=True, text=True, timeout=900)
+                        "--size", "128x160", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout
@@ -2082,9 +2083,9 @@ def test_pairs_in_flight_refuses_closures_with_shared_library_workspaces():
 
 
 def test_bench_default_command_prints_one_short_strict_json_line(tmp_path):
-    """`python bench.py --gpus 1 --steps K --warmup W` (the driver's command, every leg on, at the
-    BASELINE size) prints ONE line under 6000 bytes of strict JSON that carries the contract's keys, `roofline` and
-    `cpu_baseline`; the full record goes to the detail file the line names."""
+    """`python bench.py --gpus 1 --steps K --warmup W --full` (every leg on, at the BASELINE size)
+    prints ONE line under 6000 bytes of strict JSON that carries the contract's keys, `roofline` and `cpu_baseline`; the
+    full record goes to the detail file the line names."""
     import json
     import os
     import subprocess
@@ -2093,8 +2094,8 @@ def test_bench_default_command_prints_one_short_strict_json_line(tmp_path):
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PCFA_BENCH_DETAIL=str(tmp_path / "detail.json"))
     r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--cpu-closures", "2", "--dump-outputs", str(tmp_path / "outputs")], env=env, capture_output=True,
-                       text=True, timeout=1500)
+                        "--full", "--cpu-closures", "2", "--dump-outputs", str(tmp_path / "outputs")], env=env,
+                       capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -2123,6 +2124,49 @@ def test_bench_default_command_prints_one_short_strict_json_line(tmp_path):
     assert arrays["delta1_final"].shape == (1, 3, 440, 1024) and arrays["flow_pred_final"].shape == (1, 2, 436, 1024)
     f = detail["final"]
     assert np.allclose(arrays["step_return"], [f["aee_adv_tgt"], f["aee_adv_init"], f["l2_delta"]], rtol=1e-12)
+
+
+BENCH_FULL_ONLY = ("roofline", "roofline_unfused_lookup", "kernels", "kernel_families", "kernels_eager_step_hip_events",
+                   "kernel_rows_cover", "lbfgs", "cpu_baseline", "parity_vs_cpu_port", "calibration", "schedule_parity",
+                   "unfused_lookup_batch2", "pairs_in_flight", "shared_forward_schedule", "pwcnet", "gma", "universal")
+
+
+def test_bench_plain_command_runs_the_headline_only(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: set-up, warm-up, the timed steps, the
+    --dump-outputs files and the line with the contract's keys -- none of the records --full adds, and at most 30 s of
+    the whole run outside its warm-up and timed steps."""
+    import json
+    import subprocess
+    import sys
+    import time
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PCFA_BENCH_DETAIL=str(tmp_path / "detail.json"))
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "outputs")], env=env, capture_output=True, text=True,
+                       timeout=600)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype"):
+        assert k in out, k
+    assert out["metric"] == "attack_steps_per_sec" and out["unit"] == "attack_steps/s" and out["dtype"] == "f32"
+    assert out["higher_is_better"] is True and out["steps"] == 2 and out["warmup"] == 1
+    assert abs(out["value"] - 1e3 / out["ms_per_step"]) < 1e-6 * out["value"]
+    assert out["config"]["closure_evals_per_step"] == 10.0 and out["config"]["closure_launch"] == "hipGraph replay"
+    detail = json.load(open(env["PCFA_BENCH_DETAIL"]))
+    for k in BENCH_FULL_ONLY:
+        assert k not in out and k not in detail, k
+    assert "second_pair_same_shape" not in detail["per_pair_setup_s"]
+    d = str(tmp_path / "outputs")
+    arrays = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+    assert arrays["delta1_final"].shape == (1, 3, 440, 1024) and arrays["flow_pred_final"].shape == (1, 2, 436, 1024)
+    f = detail["final"]
+    assert np.allclose(arrays["step_return"], [f["aee_adv_tgt"], f["aee_adv_init"], f["l2_delta"]], rtol=1e-12)
+    outside = wall - (out["steps"] + out["warmup"]) * out["ms_per_step"] * 1e-3
+    assert outside < 30.0, "%.1f s outside the warm-up and timed steps" % outside
 
 
 @pytest.mark.parametrize("net,size", [("RAFT", (128, 160)), ("FlowNet2", (64, 128))])

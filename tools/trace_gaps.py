@@ -27,7 +27,7 @@ def main():
             continue  # MIOpen's one-off first-call fallback kernels of the warm-up step
         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))
     rows.sort()
-    # the busiest `window` seconds of the run = the timed steps (the tail of a bench.py run is the CPU baseline)
+    # the busiest `window` seconds of the run = the timed steps (the tail of a bench.py --full run is the CPU baseline)
     w_ns = int(window * 1e9)
     starts = [r[0] for r in rows]
     import bisect
