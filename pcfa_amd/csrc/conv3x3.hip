@@ -667,6 +667,7 @@ static int conv3x3_launch(const float* x, const float* packed, const float* bias
   // (twice the workgroups, two resident per CU)
   int mt = 1;
   if (const char* e = getenv("PCFA_CONV3X3_MT")) mt = atoi(e) == 2 ? 2 : 1;  // A/B switch for tools/dev
+  if (ksl > 1 || x2 != nullptr) mt = 1;   // (the 64-tile kernel serves neither K slices nor a second problem)
   if (mt == 2) {
     const int by2 = pcfa_cdiv(H, 16);
     grid.x = (unsigned)(blocks_x * by2);
@@ -675,13 +676,12 @@ static int conv3x3_launch(const float* x, const float* packed, const float* bias
   grid.y = Npad / 32;
   const int nchunk_all = (K + KC - 1) / KC, cper = (nchunk_all + ksl - 1) / ksl;
   if (ksl > 1) {   // K slices over workgroups: raw partial sums (the caller runs the finish pass)
-    if (x2 != nullptr || mt != 1 || bias || mask || addend || act != 0 || (cper * (ksl - 1)) >= nchunk_all) return PCFA_ERR_INVALID_ARG;
+    if (x2 != nullptr || bias || mask || addend || act != 0 || (cper * (ksl - 1)) >= nchunk_all) return PCFA_ERR_INVALID_ARG;
     grid.z = (unsigned)(B * ksl);
     if (grid.z > 65535) return PCFA_ERR_UNSUPPORTED;
   }
   Second second{x2, packed2, bias2, out2, K2, N2, (int)grid.y, mask_n, ksl, cper, PcfaXcdMap{0, 0, 0, 0}};
   if (x2 != nullptr) {
-    if (mt == 2) return PCFA_ERR_UNSUPPORTED;
     grid.y += (unsigned)((N2 + CB - 1) / CB * CB / 32);
     if (grid.y > 65535) return PCFA_ERR_UNSUPPORTED;
   }

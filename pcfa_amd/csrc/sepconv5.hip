@@ -96,6 +96,7 @@ __global__ __launch_bounds__(256 * KS) void sepconv5_kernel(Operand in, const fl
   if (in.b) in.b += (long long)blockIdx.z * (in.Cin - in.Ca) * plane;
   out.a += (long long)blockIdx.z * out.Ca * plane;
   if (out.b) out.b += (long long)blockIdx.z * (Cout - out.Ca) * plane;
+  if (out.mask_b) out.mask_b += (long long)blockIdx.z * (Cout - out.Ca) * plane;   // (shape of out.b)
 
   const int tid = threadIdx.x & 255;
   const int lane = tid & 63, wave = tid >> 6;

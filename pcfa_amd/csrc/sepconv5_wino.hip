@@ -114,6 +114,7 @@ __global__ __launch_bounds__(128 * WN * KS) void sc5_wino_kernel(Operand in, con
   if (in.b) in.b += (long long)blockIdx.z * (in.Cin - in.Ca) * plane;
   out.a += (long long)blockIdx.z * out.Ca * plane;
   if (out.b) out.b += (long long)blockIdx.z * (Cout - out.Ca) * plane;
+  if (out.mask_b) out.mask_b += (long long)blockIdx.z * (Cout - out.Ca) * plane;   // (shape of out.b)
 
   // ---- staging: every load unconditional from a clamped address, zero padding applied at the LDS write ------------
   int poff[NLOAD], pch[NLOAD], plds[NLOAD];

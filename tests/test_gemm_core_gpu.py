@@ -32,60 +32,14 @@ import torch
 import torch.nn.functional as F
 
 from pcfa_amd import _hip, hip_ops
+from tests.fenced import (DEV, FENCE, NAN_BITS, PCFA_ERR_INVALID_ARG, PCFA_ERR_UNSUPPORTED,  # noqa: F401
+                          PCFA_ERR_WORKSPACE, SENTINEL, TINY, U, Fenced, gamma)
+from tests.fenced import stream as _stream
 from tests.util import rel_l2
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda"
-U = 2.0 ** -24
-FENCE = 128 * 128               # floats of NaN / sentinel on each side of every operand: one 128x128 tile
-SENTINEL = 0x7FC0BEEF           # a quiet NaN with a payload: C elements the kernel never wrote stay non-finite
-TINY = 2.0 ** -126              # results below the fp32 normal range may be flushed to zero
-PCFA_ERR_INVALID_ARG, PCFA_ERR_UNSUPPORTED, PCFA_ERR_WORKSPACE = -1, -2, -3
 
 torch.set_num_threads(min(16, torch.get_num_threads()))
-
-
-def gamma(n):
-    return n * U / (1 - n * U)
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _span(size, stride):
-    return 1 + sum((s - 1) * st for s, st in zip(size, stride))
-
-
-class Fenced:
-    """A device buffer of `fill` bits with `view` (size, stride) placed `FENCE + shift` floats in: the operand's
-    elements are written into it, everything else keeps the fill."""
-
-    def __init__(self, size, stride, fill_bits, shift=0):
-        self.size, self.stride, self.off = tuple(size), tuple(stride), FENCE + shift
-        n = self.off + _span(size, stride) + FENCE
-        self.buf = torch.full((n,), fill_bits, dtype=torch.int32, device=DEV).view(torch.float32)
-        self.bits0 = self.buf.view(torch.int32).clone()
-        mask = torch.ones(n, dtype=torch.bool, device=DEV)
-        mask.as_strided(self.size, self.stride, self.off).fill_(False)
-        self.outside = mask
-
-    def view(self):
-        return self.buf.as_strided(self.size, self.stride, self.off)
-
-    def write(self, x):
-        self.view().copy_(x.to(DEV))
-        self.bits0 = self.buf.view(torch.int32).clone()
-        return self
-
-    def ptr(self):
-        return ctypes.c_void_p(self.buf.data_ptr() + 4 * self.off)
-
-    def fence_intact(self):
-        return torch.equal(self.buf.view(torch.int32)[self.outside], self.bits0[self.outside])
-
-
-NAN_BITS = 0x7FC00000
 
 
 def _gate(got, want64, absprod64, n, c=2.0, tiny=0.0):
