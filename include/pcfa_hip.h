@@ -458,6 +458,7 @@ PCFA_API int pcfa_conv3x3_fwd(const float* x, const float* packed, const float* 
  * models/PWCNet/PWCNet.py:29-35); pcfa_leaky_relu_bwd: grad_x = grad_out * (out > 0 ? 1 : slope). */
 PCFA_API int pcfa_conv3x3_act_fwd(const float* x, const float* packed, const float* bias, float* out, int B, int K,
                          int N, int H, int W, int act, float slope, void* stream);
+PCFA_API int pcfa_leaky_relu_fwd(const float* x, float* y, float slope, long long n, void* stream);   /* y = x > 0 ? x : x * slope */
 PCFA_API int pcfa_leaky_relu_bwd(const float* out, const float* grad_out, float* grad_x, float slope, long long n,
                         void* stream);
 /* Two independent pcfa_conv3x3_act_fwd problems over the same H x W (batch 1) in ONE launch: the motion encoder's
@@ -615,6 +616,42 @@ PCFA_API int pcfa_conv7x7_tile(int Cout, int* mt, int* cot);
 PCFA_API long long pcfa_conv7x7_packed_floats(int Cin, int Cout);
 PCFA_API int pcfa_conv7x7(const float* x, const float* mask, const float* packed, const float* bias, const float* addend,
                           float* out, int B, int Cin, int Cout, int H, int W, int relu, void* stream);
+
+/* FlowNet2's strided / transposed convolutions on the fp32 matrix cores for frozen weights (Config.flownet2_ops = "hip",
+ * models/FlowNet/submodules.py:7-36), one direct implicit GEMM in two modes:
+ *   npar = 1 (gather):  out[b][co][a][c] = act(bias[co] + sum_{ci,ty,tx} w[co][ci][ty][tx] x'[b][ci][S a + off0 + ty][S c + off0 + tx]),
+ *                       stride S = 2 with taps in {3, 4, 5, 7} (S = 1 with taps 3 also), off0 = -padding;
+ *   npar = 4 (parity):  stride 1, taps in {2, 3, 4}: output parity p = 2 ry + rx owns out[..][2 a + ry][2 c + rx] and reads
+ *                       x'[..][a + off_ry + ty][c + off_rx + tx] (off_0 = off0, off_1 = off1) with its own sub-kernel:
+ *                       ConvTranspose2d(4, 2, 1) and the data gradient of a stride-2 convolution.
+ * x' = x where mask > 0, else x * mask_slope (mask NULL: x' = x) -- the LeakyReLU backward of the layer whose gradient x is;
+ * act 2: LeakyReLU(slope), 0: none.  x / mask: [B][Cin][H][W], out: [B][Cout][OH][OW], bias: [Cout] or NULL.  `packed`
+ * (16-B aligned, pcfa_conv_gather_packed_floats floats): with (mt, cot) = pcfa_conv_gather_tile(Cout), Cout padded to cot
+ * and Cin to 4 (zeros), [npar][Cout / cot][Cin / 4][cot / mt][4 / (64 / mt)][taps][taps][64 / mt][mt] (ops.flownet2.gather_pack).
+ * Fixed summation order, no split-K, no atomics, no scratch: bitwise reproducible.  PCFA_ERR_UNSUPPORTED for other modes
+ * (pcfa_conv_gather_supported). */
+PCFA_API int pcfa_conv_gather_tile(int Cout, int* mt, int* cot);
+PCFA_API int pcfa_conv_gather_supported(int stride, int taps, int npar);
+PCFA_API long long pcfa_conv_gather_packed_floats(int Cin, int Cout, int taps, int npar);
+PCFA_API int pcfa_conv_gather(const float* x, const float* mask, float mask_slope, const float* packed, const float* bias,
+                              float* out, int B, int Cin, int H, int W, int Cout, int OH, int OW, int stride, int taps,
+                              int npar, int off0, int off1, int act, float slope, void* stream);
+
+/* Resample2d backward (kernel_size 1, bilinear; resample2d_kernel.cu:75-201) with grad_in1 as a fixed-point int64 scatter
+ * (the unit of pcfa_pwc_warp_bwd_det: 2^(floor(log2 max|grad_out|) - 40)) instead of fp32 atomics: bitwise reproducible.
+ * in1 / grad_in1: [B][C][H][W] (the flow's size), flow / grad_flow: [B][2][H][W], grad_out: [B][C][H][W];
+ * workspace >= pcfa_resample2d_bwd_det_workspace_bytes(), 8-B aligned. */
+PCFA_API size_t pcfa_resample2d_bwd_det_workspace_bytes(int B, int C, int H, int W);
+PCFA_API int pcfa_resample2d_bwd_det(const float* in1, const float* flow, const float* grad_out, float* grad_in1,
+                                     float* grad_flow, void* workspace, size_t workspace_bytes, int B, int C, int H, int W,
+                                     void* stream);
+
+/* out = nn.Upsample(scale_factor=4, mode='nearest')(div ? in / s : in * s) over `planes` planes of H x W (FlowNet2's
+ * upsample3 / upsample4); backward: grad_in = (fp32 of the fp64 sum of the 16 gradients) / s (or * s), a gather. */
+PCFA_API int pcfa_upsample_nearest4_fwd(const float* in, float* out, int planes, int H, int W, float s, int div,
+                                        void* stream);
+PCFA_API int pcfa_upsample_nearest4_bwd(const float* grad_out, float* grad_in, int planes, int H, int W, float s, int div,
+                                        void* stream);
 
 /* 3x3 / stride 1 / pad 1 convolution with N <= 4 output channels and its data gradient (frozen weights): the
  * flow-prediction layers -- FlowHead.conv2 of RAFT / GMA (models/raft/update.py:6-14), predict_flow of PWC-Net

@@ -114,6 +114,7 @@ SIGNATURES = {
     "pcfa_conv3x3_pack_weights": (c_int, [_P, _P, _P, c_int, c_int, _P]),
     "pcfa_conv3x3_fwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "pcfa_conv3x3_act_fwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P]),
+    "pcfa_leaky_relu_fwd": (c_int, [_P, _P, c_float, c_longlong, _P]),
     "pcfa_leaky_relu_bwd": (c_int, [_P, _P, _P, c_float, c_longlong, _P]),
     "pcfa_lbfgs_gram_state_bytes": (c_size_t, [c_int]),
     "pcfa_lbfgs_gram_workspace_bytes": (c_size_t, [c_int, c_longlong]),
@@ -161,6 +162,14 @@ SIGNATURES = {
     "pcfa_conv7x7_tile": (c_int, [c_int, POINTER(c_int), POINTER(c_int)]),
     "pcfa_conv7x7_packed_floats": (c_longlong, [c_int, c_int]),
     "pcfa_conv7x7": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "pcfa_conv_gather_tile": (c_int, [c_int, POINTER(c_int), POINTER(c_int)]),
+    "pcfa_conv_gather_supported": (c_int, [c_int, c_int, c_int]),
+    "pcfa_conv_gather_packed_floats": (c_longlong, [c_int, c_int, c_int, c_int]),
+    "pcfa_conv_gather": (c_int, [_P, _P, c_float, _P, _P, _P] + [c_int] * 12 + [c_int, c_float, _P]),
+    "pcfa_resample2d_bwd_det_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "pcfa_resample2d_bwd_det": (c_int, [_P, _P, _P, _P, _P, _P, c_size_t, c_int, c_int, c_int, c_int, _P]),
+    "pcfa_upsample_nearest4_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_float, c_int, _P]),
+    "pcfa_upsample_nearest4_bwd": (c_int, [_P, _P, c_int, c_int, c_int, c_float, c_int, _P]),
     "pcfa_upsample_bilinear_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
     "pcfa_upsample_bilinear_bwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
     "pcfa_instnorm_workspace_bytes": (c_size_t, [c_int, c_longlong]),

@@ -494,13 +494,15 @@ class PairsInFlight:
         all its launches share in stream order -- replayed side by side, two lanes' products use it at the same time.
         Observed (r05, tools/dev/flight_scaling.py GMA 436x1024, two lanes): the first step never returns.  The package's own
         products take their split-K scratch from the caller, so the build with gma_gemm = "hip" is safe in flight; likewise
-        SpyNet with spynet_ops = "hip" (own 7x7 convolutions and warp, no scratch shared between lanes)."""
+        SpyNet with spynet_ops = "hip" (own 7x7 convolutions and warp, no scratch shared between lanes) and FlowNet2 with
+        flownet2_ops = "hip" (own strided / transposed convolutions, no library kernel in the closure)."""
         net = getattr(getattr(attack, "args", None), "net", None)
-        if net == "FlowNet2":
-            # its closure keeps library convolutions (the transposed convolutions): the same question, never validated --
+        if net == "FlowNet2" and config.cfg(attack.model).flownet2_ops != "hip":
+            # the default build keeps library convolutions (the strided and transposed ones): never validated in flight --
             # refused rather than left to chance
-            raise ValueError("FlowNet2 keeps library convolutions inside its captured closure: several pairs in flight are "
-                             "validated for RAFT, PWCNet, GMA (gma_gemm='hip') and SpyNet (spynet_ops='hip') only")
+            raise ValueError("FlowNet2 with Config.flownet2_ops='lib' keeps library convolutions inside its captured closure "
+                             "and cannot run several pairs in flight: build the model with flownet2_ops='hip' "
+                             "(PCFA_FLOWNET2_OPS=hip) or use --pairs_in_flight 1")
         if net == "SpyNet" and config.cfg(attack.model).spynet_ops != "hip":
             # the default build runs Basic's 7x7 layers on MIOpen; the spynet_ops = "hip" build holds no library kernel
             raise ValueError("SpyNet with Config.spynet_ops='lib' keeps library convolutions inside its captured closure and "

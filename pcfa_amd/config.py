@@ -42,6 +42,10 @@ class Config:
     spynet_ops: str = "lib"              # Basic's 7x7 layers, the warp and the flow up-sampling: "lib" (MIOpen, grid_sample,
                                          # interpolate) | "hip" (ops.conv7x7, ops.spynet_warp, ops.upsample_bilinear: no library
                                          # kernel, no atomic-accumulating backward -- reproducible, allowed in flight)
+    # ---- FlowNet2 (nets/flownet2.py) ----
+    flownet2_ops: str = "lib"            # stride-2 and transposed convolutions, small-map 3x3 layers, conv_redir, Resample2d's
+                                         # backward and the x4 up-sampling: "lib" (MIOpen / ATen, fp32 atomics) | "hip"
+                                         # (ops.flownet2, ops.conv3x3 at every size: no library kernel, no atomics on float data)
     # ---- attack loop (attack_PCFA.py) ----
     reuse_pair_graphs: bool = True       # pairs of one shape share static buffers + hipGraphs
     max_cached_shapes: int = 4           # graph sets kept per model (LRU); KITTI under /8 padding has three padded shapes
@@ -54,6 +58,7 @@ class Config:
                    gma_gemm=os.environ.get("PCFA_GMA_GEMM", "lib"),
                    conv1x1=os.environ.get("PCFA_CONV1X1", "lib"),
                    spynet_ops=os.environ.get("PCFA_SPYNET_OPS", "lib"),
+                   flownet2_ops=os.environ.get("PCFA_FLOWNET2_OPS", "lib"),
                    max_cached_shapes=int(os.environ.get("PCFA_MAX_CACHED_SHAPES", "4")))
 
     def __post_init__(self):
@@ -63,6 +68,8 @@ class Config:
             raise ValueError("Config.conv1x1 must be 'lib' or 'hip', got %r" % (self.conv1x1,))
         if self.spynet_ops not in ("lib", "hip"):
             raise ValueError("Config.spynet_ops must be 'lib' or 'hip', got %r" % (self.spynet_ops,))
+        if self.flownet2_ops not in ("lib", "hip"):
+            raise ValueError("Config.flownet2_ops must be 'lib' or 'hip', got %r" % (self.flownet2_ops,))
         if self.max_cached_shapes < 1:
             raise ValueError("Config.max_cached_shapes must be >= 1")
 

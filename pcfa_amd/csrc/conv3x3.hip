@@ -493,6 +493,11 @@ __global__ void leaky_relu_bwd_kernel(const float* __restrict__ out, const float
     gx[i] = out[i] > 0.f ? g[i] : g[i] * slope;
 }
 
+__global__ void leaky_relu_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, float slope, long long n) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    y[i] = x[i] > 0.f ? x[i] : x[i] * slope;
+}
+
 #ifdef PCFA_C3_STAMPS
 extern "C" __attribute__((visibility("default"))) int dev_c3_stamps(unsigned long long* host8, int reset) {
   if (hipMemcpyFromSymbol(host8, HIP_SYMBOL(c3_stamp_sums), 8 * sizeof(unsigned long long)) != hipSuccess) return -1;
@@ -503,6 +508,14 @@ extern "C" __attribute__((visibility("default"))) int dev_c3_stamps(unsigned lon
   return 0;
 }
 #endif
+
+extern "C" int pcfa_leaky_relu_fwd(const float* x, float* y, float slope, long long n, void* stream) {
+  if (!x || !y || n < 1) return PCFA_ERR_INVALID_ARG;
+  pcfa_launch(leaky_relu_fwd_kernel, dim3((unsigned)min((n + 255) / 256, 4096LL)), dim3(256), 0, (hipStream_t)stream, x, y,
+              slope, n);
+  PCFA_LAUNCH_CHECK();
+  return PCFA_OK;
+}
 
 extern "C" int pcfa_leaky_relu_bwd(const float* out, const float* grad_out, float* grad_x, float slope, long long n,
                                    void* stream) {

@@ -22,6 +22,7 @@
 // Other parameter sets (odd kernel_size, any stride2 / pad; stride1 = 1 for the backward) take one-thread-per-
 // element kernels that restate the reference loops.
 #include "common.hpp"
+#include "resample2d_taps.hpp"
 
 namespace {
 
@@ -378,23 +379,6 @@ __global__ __launch_bounds__(FH* FW) void fcorr_bwd_fast_kernel(const float* __r
 // Resample2d (kernel_size 1): out[b][c][y][x] = bilinear(in1[b][c], x + flow_x, y + flow_y), the four neighbour
 // indices clamped to the image one by one (resample2d_kernel.cu:44-62).
 // ---------------------------------------------------------------------------------------------------------
-struct RsTaps {
-  int xL, xR, yT, yB;
-  float alpha, beta;
-};
-
-__device__ __forceinline__ RsTaps rs_taps(float xf, float yf, int h, int w) {
-  RsTaps t;
-  const float fx = floorf(xf), fy = floorf(yf);
-  t.alpha = xf - fx;
-  t.beta = yf - fy;
-  t.xL = max(min((int)fx, w - 1), 0);
-  t.xR = max(min((int)(fx + 1.f), w - 1), 0);
-  t.yT = max(min((int)fy, h - 1), 0);
-  t.yB = max(min((int)(fy + 1.f), h - 1), 0);
-  return t;
-}
-
 __global__ void resample2d_fwd_kernel(const float* __restrict__ in1, const float* __restrict__ flow,
                                       float* __restrict__ out, int B, int C, int iH, int iW, int H, int W,
                                       int bilinear) {

@@ -161,6 +161,34 @@ __global__ void convex_upsample_gflow_kernel(const float* __restrict__ T, float*
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// nn.Upsample(scale_factor=4, mode='nearest') of (x * s) or (x / s): FlowNet2's upsample3 / upsample4 (FlowNet2.py:152,160)
+// with the scalar applied first, as the reference forms it (out[Y][X] = x[Y / 4][X / 4] op s).  Backward: a gather of the 16
+// gradients of each input pixel, summed in fp64 and rounded once (no atomics, no ATen backward), then op s as autograd's
+// mul / div backward does.
+__global__ __launch_bounds__(256) void upsample_nearest4_fwd_kernel(const float* __restrict__ in, float* __restrict__ out,
+                                                                    int H, int W, float s, int div) {
+  const int OW = 4 * W, OH = 4 * H;
+  const int X = blockIdx.x * 256 + threadIdx.x, Y = blockIdx.y;
+  if (X >= OW) return;
+  const float v = in[((size_t)blockIdx.z * H + (Y >> 2)) * W + (X >> 2)];
+  out[((size_t)blockIdx.z * OH + Y) * OW + X] = div ? v / s : v * s;
+}
+
+__global__ __launch_bounds__(256) void upsample_nearest4_bwd_kernel(const float* __restrict__ gout, float* __restrict__ gin,
+                                                                    int H, int W, float s, int div) {
+  const int OW = 4 * W;
+  const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+  if (x >= W) return;
+  const float* gp = gout + ((size_t)blockIdx.z * 4 * H + 4 * y) * OW + 4 * x;
+  double acc = 0.0;
+#pragma unroll
+  for (int dy = 0; dy < 4; ++dy)
+#pragma unroll
+    for (int dx = 0; dx < 4; ++dx) acc += (double)gp[(size_t)dy * OW + dx];
+  const float t = (float)acc;
+  gin[((size_t)blockIdx.z * H + y) * W + x] = div ? t / s : t * s;
+}
+
 }  // namespace
 
 extern "C" int pcfa_convex_upsample_fwd(const float* flow, const float* mask, float* out, int N, int H, int W,
@@ -279,6 +307,27 @@ extern "C" int pcfa_upsample_bilinear_bwd(const float* grad_out, float* grad_in,
   dim3 grid(pcfa_cdiv(W, 256), H, planes);
   pcfa_launch(upsample_bilinear_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, grad_out, grad_in, H, W, factor,
               1.0f / (float)factor, mul);
+  PCFA_LAUNCH_CHECK();
+  return PCFA_OK;
+}
+
+extern "C" int pcfa_upsample_nearest4_fwd(const float* in, float* out, int planes, int H, int W, float s, int div,
+                                          void* stream) {
+  if (!in || !out || planes < 1 || H < 1 || W < 1 || (div && s == 0.f)) return PCFA_ERR_INVALID_ARG;
+  if (planes > 65535 || (long long)H * 4 > 65535) return PCFA_ERR_UNSUPPORTED;
+  dim3 grid(pcfa_cdiv((long long)W * 4, 256), H * 4, planes);
+  pcfa_launch(upsample_nearest4_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, in, out, H, W, s, div ? 1 : 0);
+  PCFA_LAUNCH_CHECK();
+  return PCFA_OK;
+}
+
+extern "C" int pcfa_upsample_nearest4_bwd(const float* grad_out, float* grad_in, int planes, int H, int W, float s, int div,
+                                          void* stream) {
+  if (!grad_out || !grad_in || planes < 1 || H < 1 || W < 1 || (div && s == 0.f)) return PCFA_ERR_INVALID_ARG;
+  if (planes > 65535 || H > 65535) return PCFA_ERR_UNSUPPORTED;
+  dim3 grid(pcfa_cdiv(W, 256), H, planes);
+  pcfa_launch(upsample_nearest4_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, grad_out, grad_in, H, W, s,
+              div ? 1 : 0);
   PCFA_LAUNCH_CHECK();
   return PCFA_OK;
 }

@@ -14,6 +14,7 @@
 // original PWC-Net code), the sample position is x * W / (W - 1) - 0.5.
 #include <cstdlib>
 #include "common.hpp"
+#include "resample2d_taps.hpp"
 
 namespace {
 
@@ -559,6 +560,61 @@ int warp_bwd_det(const float* x, const float* flo, const float* grad_out, float*
   return PCFA_OK;
 }
 
+// FlowNet2's Resample2d backward (resample2d_kernel.cu:75-201) with grad_in1 through the fixed-point scatter above instead
+// of fp32 atomics: one thread per output pixel, the reference's coordinates (x + flow_x, y + flow_y), neighbours clamped
+// against the input size, truncation weights (xf - int(xf)), each addend the same fp32 product as the atomic kernel of
+// flownet_ops.hip forms, rounded once to the call's fixed-point unit.  The flow gradient is the reference's gather, written
+// directly (one thread owns every channel of its pixel).  in1 has the flow's size (FlowNet2 warps full-size images).
+__global__ __launch_bounds__(256) void resample2d_bwd_det_kernel(const float* __restrict__ in1, const float* __restrict__ flow,
+                                                                const float* __restrict__ gout, long long* __restrict__ gxi,
+                                                                float* __restrict__ gflow, const float* __restrict__ bmax,
+                                                                int nblk, int B, int C, int H, int W) {
+  __shared__ float red[4];
+  const double scale = ldexp(1.0, warp_fix_shift(bmax, nblk, red));   // (block-wide: before any thread leaves)
+  const long long total = (long long)B * H * W;
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int x = idx % W, y = (idx / W) % H, b = (int)(idx / ((long long)W * H));
+  const size_t plane = (size_t)H * W;
+  const float dx = flow[((size_t)b * 2) * plane + (size_t)y * W + x];
+  const float dy = flow[((size_t)b * 2 + 1) * plane + (size_t)y * W + x];
+  const float xf = (float)x + dx, yf = (float)y + dy;
+  const RsTaps t1 = rs_taps(xf, yf, H, W);
+  const float a1 = xf - (float)(int)xf, b1 = yf - (float)(int)yf;
+  const RsTaps& t2 = t1;   // the flow gradient clamps against the flow size: the same here
+  const float gam_x = 1.f - t2.alpha, gam_y = 1.f - t2.beta;
+  const float* src = in1 + (size_t)b * C * plane;
+  const float* g = gout + (size_t)b * C * plane + (size_t)y * W + x;
+  long long* d1 = gxi + (size_t)b * C * plane;
+  float gdx = 0.f, gdy = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const float gv = g[(size_t)c * plane];
+    long long* d = d1 + (size_t)c * plane;
+    fix_add(d + (size_t)t1.yT * W + t1.xL, (1.f - a1) * (1.f - b1) * gv, scale);
+    fix_add(d + (size_t)t1.yT * W + t1.xR, a1 * (1.f - b1) * gv, scale);
+    fix_add(d + (size_t)t1.yB * W + t1.xL, (1.f - a1) * b1 * gv, scale);
+    fix_add(d + (size_t)t1.yB * W + t1.xR, a1 * b1 * gv, scale);
+    const float* s = src + (size_t)c * plane;
+    const float iTL = s[(size_t)t2.yT * W + t2.xL], iTR = s[(size_t)t2.yT * W + t2.xR];
+    const float iBL = s[(size_t)t2.yB * W + t2.xL], iBR = s[(size_t)t2.yB * W + t2.xR];
+    gdx += gam_y * gv * iTR;
+    gdx -= gam_y * gv * iTL;
+    gdx += (1.f - gam_y) * gv * iBR;
+    gdx -= (1.f - gam_y) * gv * iBL;
+    gdy += gam_x * gv * iBL;
+    gdy -= gam_x * gv * iTL;
+    gdy += (1.f - gam_x) * gv * iBR;
+    gdy -= (1.f - gam_x) * gv * iTR;
+  }
+  gflow[((size_t)b * 2) * plane + (size_t)y * W + x] = gdx;
+  gflow[((size_t)b * 2 + 1) * plane + (size_t)y * W + x] = gdy;
+}
+
+size_t resample2d_bwd_det_workspace_bytes(int B, int C, int H, int W) {
+  if (B < 1 || C < 1 || H < 1 || W < 1) return 0;
+  return (size_t)B * C * H * W * sizeof(long long) + WARP_BMAX * sizeof(float);
+}
+
 }  // namespace
 
 extern "C" int pcfa_pwc_warp_fwd(const float* x, const float* flo, float* out, int B, int C, int H, int W,
@@ -616,6 +672,35 @@ extern "C" int pcfa_pwc_warp_bwd(const float* x, const float* flo, const float* 
   dim3 grid(pcfa_cdiv(plane, 256), channel_groups(plane, C), B);
   pcfa_launch(pwc_warp_bwd_kernel, grid, dim3(256), 0, s, x, flo, grad_out, grad_x, grad_flo, C, H, W,
               mask_threshold, flow_scale);
+  PCFA_LAUNCH_CHECK();
+  return PCFA_OK;
+}
+
+extern "C" size_t pcfa_resample2d_bwd_det_workspace_bytes(int B, int C, int H, int W) {
+  return resample2d_bwd_det_workspace_bytes(B, C, H, W);
+}
+
+extern "C" int pcfa_resample2d_bwd_det(const float* in1, const float* flow, const float* grad_out, float* grad_in1,
+                                       float* grad_flow, void* workspace, size_t workspace_bytes, int B, int C, int H, int W,
+                                       void* stream) {
+  if (!in1 || !flow || !grad_out || !grad_in1 || !grad_flow || !workspace || B < 1 || C < 1 || H < 1 || W < 1)
+    return PCFA_ERR_INVALID_ARG;
+  if (workspace_bytes < resample2d_bwd_det_workspace_bytes(B, C, H, W)) return PCFA_ERR_WORKSPACE;
+  if (reinterpret_cast<uintptr_t>(workspace) & 7) return PCFA_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const long long nx = (long long)B * C * H * W, total = (long long)B * H * W;
+  long long* gxi = (long long*)workspace;
+  float* bmax = (float*)(gxi + nx);
+  const int nblk = (int)min((nx + 255) / 256, (long long)WARP_BMAX);
+  pcfa_launch(zero_ll_max_kernel, dim3(nblk), dim3(256), 0, s, gxi, grad_out, bmax, nx);
+  PCFA_LAUNCH_CHECK();
+  pcfa_launch(resample2d_bwd_det_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in1, flow, grad_out, gxi,
+              grad_flow, (const float*)bmax, nblk, B, C, H, W);
+  PCFA_LAUNCH_CHECK();
+  // grad_in1 = fixed point * unit, in index order (no flow partials: nf = 0)
+  pcfa_launch(pwc_warp_finish_kernel, dim3((int)min((nx + 255) / 256, 4096LL)), dim3(256), 0, s, (const long long*)gxi,
+              (const float*)nullptr, (const float*)bmax, nblk, grad_in1, (float*)nullptr, nx, 0LL, 1, 1.f, 1.f,
+              (long long)H * W);
   PCFA_LAUNCH_CHECK();
   return PCFA_OK;
 }

@@ -12,12 +12,20 @@ div_flow=20 (helper_functions/ownutilities.py:147-155); so does this file.
 The three CUDA-only extensions of the reference (correlation_cuda, resample2d_cuda, channelnorm_cuda) are the HIP
 operators `flownet_correlation`, `resample2d`, `channelnorm` of pcfa_amd.ops; frozen 3x3 / stride-1 convolutions
 run as ops.conv3x3 (Winograd on the fp32 matrix cores, bias + LeakyReLU in the epilogue).
+
+Config.flownet2_ops = "hip" (opt-in) runs the rest on the package's kernels as well: the stride-2 convolutions
+(ops.conv_s2_leaky), the transposed ones (ops.deconv4s2_leaky; the 2->2 upsampled_flow layers on ops.deconv4s2_fewout),
+every stride-1 3x3 layer on ops.conv3x3 whatever the map size, conv_redir on ops.conv1x1 + ops.leaky_relu, Resample2d
+with a fixed-point backward (ops.resample2d_det) and the x4 up-sampling (ops.upsample_bilinear, ops.upsample_nearest4).
+The closure then holds no library convolution and no atomic-accumulating backward: reproducible bit for bit, allowed in
+flight.  A layer no own kernel covers raises ValueError; nothing falls back to the library.
 """
 import torch
 import torch.nn as nn
 from torch.nn import init
 
 from .. import ops
+from ..config import cfg
 
 # ops.conv3x3 works on 8x16-pixel tiles x 32 output channels; below this many pixels the grid cannot fill the chip
 _CONV3X3_MIN_PIXELS = 1024
@@ -29,11 +37,39 @@ def _hip_conv_ok(c, x):
             and not c.weight.requires_grad and not (c.bias is not None and c.bias.requires_grad))
 
 
+def _hip(module, x):
+    return cfg(module).flownet2_ops == "hip" and x.is_cuda
+
+
+def _frozen(c):
+    if c.weight.requires_grad or (c.bias is not None and c.bias.requires_grad):
+        raise ValueError("FlowNet2 with flownet2_ops='hip' runs frozen weights only (%s)" % (c,))
+
+
+def _hip_conv(c, x, slope):
+    """The flownet2_ops = "hip" route of one Conv2d (+ LeakyReLU(slope) unless slope is None)."""
+    _frozen(c)
+    o = ops.get()
+    k, s = c.kernel_size, c.stride
+    if k[0] == k[1] and c.padding == (k[0] // 2,) * 2 and c.dilation == (1, 1) and c.groups == 1:
+        if k == (3, 3) and s == (1, 1):
+            return o.conv3x3(x, c.weight, c.bias, False, slope)
+        if s == (2, 2) and slope is not None and o.conv_s2_leaky_covers(k[0], x.shape[2], x.shape[3]):
+            return o.conv_s2_leaky(x, c.weight, c.bias, slope)
+        if k == (1, 1) and s == (1, 1):
+            y = o.conv1x1(x, c.weight, c.bias)
+            return y if slope is None else o.leaky_relu(y, slope)
+    raise ValueError("FlowNet2 with flownet2_ops='hip': no own kernel for %s on a %dx%d map"
+                     % (c, x.shape[2], x.shape[3]))
+
+
 class _ConvLeaky(nn.Sequential):
     """conv(batchNorm=False, ...) of submodules.py:7-19: Conv2d + LeakyReLU(0.1), parameter names "0.weight"/"0.bias"."""
 
     def forward(self, x):
         c = self[0]
+        if _hip(self, x):
+            return _hip_conv(c, x, self[1].negative_slope)
         if _hip_conv_ok(c, x):
             return ops.get().conv3x3(x, c.weight, c.bias, False, self[1].negative_slope)
         return super().forward(x)
@@ -44,6 +80,8 @@ class _ConvLinear(nn.Sequential):
 
     def forward(self, x):
         c = self[0]
+        if _hip(self, x):
+            return _hip_conv(c, x, None)
         if _hip_conv_ok(c, x):
             return ops.get().conv3x3(x, c.weight, c.bias, False)
         return super().forward(x)
@@ -76,9 +114,34 @@ def predict_flow(in_planes):
     return _PredictFlow(in_planes, 2, kernel_size=3, stride=1, padding=1, bias=True)
 
 
+class _DeconvLeaky(nn.Sequential):
+    """deconv() of submodules.py:36: ConvTranspose2d(4, 2, 1) + LeakyReLU(0.1), parameter names "0.weight"/"0.bias"."""
+
+    def forward(self, x):
+        if _hip(self, x):
+            _frozen(self[0])
+            return ops.get().deconv4s2_leaky(x, self[0].weight, self[0].bias, self[1].negative_slope)
+        return super().forward(x)
+
+
 def deconv(in_planes, out_planes):
-    return nn.Sequential(nn.ConvTranspose2d(in_planes, out_planes, kernel_size=4, stride=2, padding=1, bias=True),
-                         nn.LeakyReLU(0.1))
+    return _DeconvLeaky(nn.ConvTranspose2d(in_planes, out_planes, kernel_size=4, stride=2, padding=1, bias=True),
+                        nn.LeakyReLU(0.1))
+
+
+class _UpsampleFlow(nn.ConvTranspose2d):
+    """The 2->2 upsampled_flow* layers (ConvTranspose2d(2, 2, 4, 2, 1)); with flownet2_ops = "hip" on PWC-Net's
+    deconv4s2_fewout (a streaming kernel, fixed summation order)."""
+
+    def forward(self, x):
+        if _hip(self, x):
+            _frozen(self)
+            return ops.get().deconv4s2_fewout(x, self.weight, self.bias)
+        return super().forward(x)
+
+
+def upsampled_flow(bias=True):
+    return _UpsampleFlow(2, 2, 4, 2, 1, bias=bias)
 
 
 def _init(module):
@@ -104,7 +167,7 @@ class _Refinement:
         self.predict_flow3 = predict_flow(386)
         self.predict_flow2 = predict_flow(194)
         for name in ("6_to_5", "5_to_4", "4_to_3", "3_to_2"):
-            setattr(self, "upsampled_flow" + name, nn.ConvTranspose2d(2, 2, 4, 2, 1, bias=flow_bias))
+            setattr(self, "upsampled_flow" + name, upsampled_flow(bias=flow_bias))
 
     def _decode(self, out_conv2, out_conv3, out_conv4, out_conv5, out_conv6):
         flow6 = self.predict_flow6(out_conv6)
@@ -217,7 +280,7 @@ class FlowNetSD(nn.Module):
         self.predict_flow3 = predict_flow(128)
         self.predict_flow2 = predict_flow(64)
         for name in ("6_to_5", "5_to_4", "4_to_3", "3_to_2"):
-            setattr(self, "upsampled_flow" + name, nn.ConvTranspose2d(2, 2, 4, 2, 1))
+            setattr(self, "upsampled_flow" + name, upsampled_flow())
         _init(self)
 
     def forward(self, x):
@@ -260,8 +323,8 @@ class FlowNetFusion(nn.Module):
         self.predict_flow2 = predict_flow(128)
         self.predict_flow1 = predict_flow(32)
         self.predict_flow0 = predict_flow(16)
-        self.upsampled_flow2_to_1 = nn.ConvTranspose2d(2, 2, 4, 2, 1)
-        self.upsampled_flow1_to_0 = nn.ConvTranspose2d(2, 2, 4, 2, 1)
+        self.upsampled_flow2_to_1 = upsampled_flow()
+        self.upsampled_flow1_to_0 = upsampled_flow()
         _init(self)
 
     def forward(self, x):
@@ -293,35 +356,48 @@ class FlowNet2(nn.Module):
         self.flownetfusion = FlowNetFusion()
         _init(self)
 
-    def _warp_block(self, x, flow):
+    def _warp_block(self, x, flow, hip=False):
         """Warp image 2 towards image 1 and take the brightness error (FlowNet2.py:128-134)."""
         o = ops.get()
-        resampled = o.resample2d(x[:, 3:, :, :], flow)
+        resampled = o.resample2d_det(x[:, 3:, :, :], flow) if hip else o.resample2d(x[:, 3:, :, :], flow)
         norm_diff = o.channelnorm(x[:, :3, :, :] - resampled)
         return resampled, norm_diff
 
     def forward(self, inputs):
         o = ops.get()
+        hip = _hip(self, inputs)
         rgb_mean = inputs.contiguous().view(inputs.size()[:2] + (-1,)).mean(dim=-1).view(
             inputs.size()[:2] + (1, 1, 1,))
         x = (inputs - rgb_mean) / self.rgb_max
         x = torch.cat((x[:, :, 0, :, :], x[:, :, 1, :, :]), dim=1)
 
-        flownetc_flow = self.upsample1(self.flownetc(x)[0] * self.div_flow)
-        resampled_img1, norm_diff_img0 = self._warp_block(x, flownetc_flow)
+        if hip:
+            flownetc_flow = o.upsample_bilinear(self.flownetc(x)[0], 4, self.div_flow)
+        else:
+            flownetc_flow = self.upsample1(self.flownetc(x)[0] * self.div_flow)
+        resampled_img1, norm_diff_img0 = self._warp_block(x, flownetc_flow, hip)
         concat1 = torch.cat((x, resampled_img1, flownetc_flow / self.div_flow, norm_diff_img0), dim=1)
 
-        flownets1_flow = self.upsample2(self.flownets_1(concat1)[0] * self.div_flow)
-        resampled_img1, norm_diff_img0 = self._warp_block(x, flownets1_flow)
+        if hip:
+            flownets1_flow = o.upsample_bilinear(self.flownets_1(concat1)[0], 4, self.div_flow)
+        else:
+            flownets1_flow = self.upsample2(self.flownets_1(concat1)[0] * self.div_flow)
+        resampled_img1, norm_diff_img0 = self._warp_block(x, flownets1_flow, hip)
         concat2 = torch.cat((x, resampled_img1, flownets1_flow / self.div_flow, norm_diff_img0), dim=1)
 
-        flownets2_flow = self.upsample4(self.flownets_2(concat2)[0] * self.div_flow)
+        if hip:
+            flownets2_flow = o.upsample_nearest4(self.flownets_2(concat2)[0], self.div_flow)
+        else:
+            flownets2_flow = self.upsample4(self.flownets_2(concat2)[0] * self.div_flow)
         norm_flownets2_flow = o.channelnorm(flownets2_flow)
-        _, diff_flownets2_img1 = self._warp_block(x, flownets2_flow)
+        _, diff_flownets2_img1 = self._warp_block(x, flownets2_flow, hip)
 
-        flownetsd_flow = self.upsample3(self.flownets_d(x)[0] / self.div_flow)
+        if hip:
+            flownetsd_flow = o.upsample_nearest4(self.flownets_d(x)[0], self.div_flow, div=True)
+        else:
+            flownetsd_flow = self.upsample3(self.flownets_d(x)[0] / self.div_flow)
         norm_flownetsd_flow = o.channelnorm(flownetsd_flow)
-        _, diff_flownetsd_img1 = self._warp_block(x, flownetsd_flow)
+        _, diff_flownetsd_img1 = self._warp_block(x, flownetsd_flow, hip)
 
         concat3 = torch.cat((x[:, :3, :, :], flownetsd_flow, flownets2_flow, norm_flownetsd_flow,
                              norm_flownets2_flow, diff_flownetsd_img1, diff_flownets2_img1), dim=1)

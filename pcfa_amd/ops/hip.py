@@ -9,6 +9,9 @@ Operator boundaries mirrored (reference file:line) -- one module per group:
   pwc          spatial_correlation_sample, pwc_cost_volume    .../spatial_correlation_sampler/spatial_correlation_sampler.py:9-91
                pwc_warp, deconv4s2_fewout, upsample_bilinear  models/PWCNet/PWCNet.py:166-206, :42-43, :73,321
   flownet      flownet_correlation, resample2d, channelnorm   models/FlowNet/{correlation,resample2d,channelnorm}_package/*.py
+  flownet2     conv_s2_leaky, deconv4s2_leaky, resample2d_det, upsample_nearest4, leaky_relu
+                                                              models/FlowNet/submodules.py:7-36, FlowNet2.py:115-177
+                                                              (Config.flownet2_ops = "hip")
   conv         conv3x3, conv3x3_cat, dense_block, conv_s2(_ds), conv_fewin, conv3x3_fewout, sepconv5,
                instance_norm_relu, add_relu                   models/raft/update.py, extractor.py, PWCNet.py:29-38,234-323
   gru          gru_step, gru_gates(_packed), gru_update, bias_relu, fanout, flow_step, convex_upsample
@@ -29,6 +32,7 @@ from .core import _call, _dev, _ptr, _ptr_off, _stream  # noqa: F401
 from .corr import *  # noqa: F401,F403
 from .corr import _convc1_packed  # noqa: F401
 from .flownet import *  # noqa: F401,F403
+from .flownet2 import *  # noqa: F401,F403
 from .gma import *  # noqa: F401,F403
 from .gru import *  # noqa: F401,F403
 from .profiling import *  # noqa: F401,F403
