@@ -150,6 +150,29 @@ PCFA_API int pcfa_corr_lookup_fwd(const float* pyr, const float* coords, float* 
 PCFA_API int pcfa_corr_lookup_bwd(float* dpyr, const float* coords, const float* grad_out, int B, int H,
                          int W, int num_levels, int radius, void* stream);
 
+/* RAFT / GMA correlation on demand (Config.corr = "on_demand"; the arithmetic of the reference's AlternateCorrBlock,
+ * models/raft/corr.py:63-91): the all-pairs pyramid is never formed.  Memory O(B*Q*D) instead of O(B*Q^2).
+ * prepare: once per forward -- channels-last fmap1 and the average-pooled pyramid of fmap2 (F.avg_pool2d(., 2, 2),
+ *   floor) into `workspace` (>= pcfa_corr_ondemand_workspace_bytes(); host-only, 0 = shape not served).
+ * fwd: out [B][L*(2r+1)^2][H][W] for coords [B][2][H][W], channel order and sampling exactly those of
+ *   pcfa_corr_lookup_fwd; each window dot product is scaled by 1/sqrt(D) before the bilinear blend.
+ * bwd: one lookup's gradient; accumulate = 0 for the first lookup of a backward pass (starts the sums), 1 after.
+ *   dfmap1 is summed per query in fp32 (no atomics), the fmap2 side through a per-call-scaled fixed-point int64 scatter
+ *   (integer adds: deterministic, run-to-run identical bits).  A non-finite grad_out or fmap1 makes all of dfmap2 NaN.
+ * finish: once per backward, after the last bwd: dfmap1, dfmap2 [B][D][H][W] (adjoint of the pooling summed over the
+ *   levels; overwritten, no pre-zeroing).
+ * Served: D % 4 == 0, 4 <= D <= 512, radius 1..4, every level at least 1x1 (PCFA_ERR_UNSUPPORTED otherwise).
+ * Offsets are 64-bit throughout. */
+PCFA_API size_t pcfa_corr_ondemand_workspace_bytes(int B, int D, int H, int W, int num_levels);
+PCFA_API int pcfa_corr_ondemand_prepare(const float* fmap1, const float* fmap2, void* workspace, int B, int D, int H,
+                               int W, int num_levels, void* stream);
+PCFA_API int pcfa_corr_ondemand_fwd(const void* workspace, const float* coords, float* out, int B, int D, int H, int W,
+                           int num_levels, int radius, void* stream);
+PCFA_API int pcfa_corr_ondemand_bwd(void* workspace, const float* coords, const float* grad_out, int accumulate, int B,
+                           int D, int H, int W, int num_levels, int radius, void* stream);
+PCFA_API int pcfa_corr_ondemand_finish(const void* workspace, float* dfmap1, float* dfmap2, int B, int D, int H, int W,
+                              int num_levels, void* stream);
+
 /* GMA attention products and softmax (models/gma/gma.py:34-77 Attention, :79-115 Aggregate).
  * pcfa_gemm_f32: C[b][m][n] = alpha * sum_k A(m,k) B(k,n) on the fp32 matrix cores (the pyramid's GEMM core, exact
  * fp32 products).  a_kmajor 0: A stored [M][K] (lda = row stride), 1: stored [K][M]; b_kmajor 0: B stored [N][K],

@@ -30,6 +30,8 @@ class Config:
     gma_gemm: str = "lib"                # GMA attention products: "lib" (rocBLAS through torch.matmul) | "hip" (pcfa_gemm_f32)
     conv1x1: str = "lib"                 # the encoders' output layer and the mask head's 1x1 layer: "lib" | "hip" (pcfa_gemm_f32:
                                          # a RAFT closure then holds no library kernel at all)
+    corr: str = "all_pairs"              # correlation: "all_pairs" (CorrBlock: O(Q^2) pyramid, fused lookup -> convc1) |
+                                         # "on_demand" (OnDemandCorrBlock: window dot products per lookup, O(Q*D) memory)
     # ---- PWC-Net (nets/pwcnet.py) ----
     dilated_as_subgrids: tuple = (2, 4, 8, 16)   # dilations run as d*d plain 3x3 convolutions on sub-grids (() = library)
     deconv_fewout: bool = True           # deconv / upfeat layers and the x4 up-sampling on own deterministic kernels
@@ -57,6 +59,7 @@ class Config:
                    defer_relu=_env_bool("PCFA_DEFER_RELU", True),
                    gma_gemm=os.environ.get("PCFA_GMA_GEMM", "lib"),
                    conv1x1=os.environ.get("PCFA_CONV1X1", "lib"),
+                   corr=os.environ.get("PCFA_CORR", "all_pairs"),
                    spynet_ops=os.environ.get("PCFA_SPYNET_OPS", "lib"),
                    flownet2_ops=os.environ.get("PCFA_FLOWNET2_OPS", "lib"),
                    max_cached_shapes=int(os.environ.get("PCFA_MAX_CACHED_SHAPES", "4")))
@@ -66,6 +69,8 @@ class Config:
             raise ValueError("Config.gma_gemm must be 'lib' or 'hip', got %r" % (self.gma_gemm,))
         if self.conv1x1 not in ("lib", "hip"):
             raise ValueError("Config.conv1x1 must be 'lib' or 'hip', got %r" % (self.conv1x1,))
+        if self.corr not in ("all_pairs", "on_demand"):
+            raise ValueError("Config.corr must be 'all_pairs' or 'on_demand', got %r" % (self.corr,))
         if self.spynet_ops not in ("lib", "hip"):
             raise ValueError("Config.spynet_ops must be 'lib' or 'hip', got %r" % (self.spynet_ops,))
         if self.flownet2_ops not in ("lib", "hip"):

@@ -5,6 +5,8 @@ Behavioural reference (cv-stuttgart/PCFA):
     models/gma/gma.py:7-115          RelPosEmb, Attention, Aggregate
     models/gma/update.py:112-139     GMAUpdateBlock
     models/gma/corr.py:15-63         -> pcfa_amd.ops.get().CorrBlock (same HIP kernels as RAFT)
+                                        or OnDemandCorrBlock under Config.corr = "on_demand" (O(Q*D) memory;
+                                        the attention stays O(Q^2), and in flight GMA still needs gma_gemm = "hip")
 
 Parameter names follow the public gma-sintel.pth checkpoint.  The reference
 config enables fp16 autocast on CUDA (models/_config/gma_config.json:5); the CPU
@@ -190,8 +192,11 @@ class RAFTGMA(nn.Module):
         hdim, cdim = self.hidden_dim, self.context_dim
 
         fmap1, fmap2 = self.fnet(images12, split=image1.shape[0])
-        corr_fn = ops.get().CorrBlock(_f32(fmap1), _f32(fmap2), num_levels=4, radius=self.args.corr_radius,
-                                      bwd_windows=cfg(self).pyramid_bwd_windows)
+        if cfg(self).corr == "on_demand":   # O(Q*D) correlation; the attention below stays O(Q^2)
+            corr_fn = ops.get().OnDemandCorrBlock(_f32(fmap1), _f32(fmap2), num_levels=4, radius=self.args.corr_radius)
+        else:
+            corr_fn = ops.get().CorrBlock(_f32(fmap1), _f32(fmap2), num_levels=4, radius=self.args.corr_radius,
+                                          bwd_windows=cfg(self).pyramid_bwd_windows)
 
         net, inp = torch.split(self.cnet(image1), [hdim, cdim], dim=1)
         net, inp = torch.tanh(net), torch.relu(inp)

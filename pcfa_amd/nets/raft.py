@@ -7,6 +7,7 @@ prefix.  Behavioural reference (cv-stuttgart/PCFA):
     models/raft/extractor.py:6-58,118-192   residual encoder
     models/raft/update.py:6-16,33-60,79-136 motion encoder, SepConvGRU, heads
     models/raft/corr.py:12-60       -> pcfa_amd.ops.get().CorrBlock (HIP)
+    models/raft/corr.py:63-91       -> pcfa_amd.ops.get().OnDemandCorrBlock under Config.corr = "on_demand"
 
 Differences that do not change results:
   * convolutions / norms run on MIOpen through torch; the all-pairs volume,
@@ -398,7 +399,13 @@ class LookupRef:
             out = fused(self.coords, conv.weight, conv.bias, True)
             if out is not None:
                 return out
-        return _conv_relu(conv, self.tensor())
+        x = self.tensor()
+        c = cfg(conv)
+        if c.corr == "on_demand" and c.conv1x1 == "hip" and x.is_cuda and _is_plain1x1(conv) and _frozen_conv(conv):
+            # no fused on-demand form: convc1 on the materialised lookup through the package's own 1x1 product (no
+            # library kernel), then bias + ReLU in one pass
+            return ops.get().bias_relu(ops.get().conv1x1(x, conv.weight, None), conv.bias)
+        return _conv_relu(conv, x)
 
 
 class BasicMotionEncoder(nn.Module):
@@ -539,8 +546,12 @@ class RAFT(nn.Module):
             with torch.cuda.stream(side):
                 cnet_out = self.cnet(image1)
         fmap1, fmap2 = self.fnet(images12, split=image1.shape[0])
-        corr_fn = ops.get().CorrBlock(_f32(fmap1), _f32(fmap2), num_levels=self.args["corr_levels"],
-                                      radius=self.args["corr_radius"], bwd_windows=cfg(self).pyramid_bwd_windows)
+        if cfg(self).corr == "on_demand":
+            corr_fn = ops.get().OnDemandCorrBlock(_f32(fmap1), _f32(fmap2), num_levels=self.args["corr_levels"],
+                                                  radius=self.args["corr_radius"])
+        else:
+            corr_fn = ops.get().CorrBlock(_f32(fmap1), _f32(fmap2), num_levels=self.args["corr_levels"],
+                                          radius=self.args["corr_radius"], bwd_windows=cfg(self).pyramid_bwd_windows)
         if side is not None:
             main.wait_stream(side)
         else:

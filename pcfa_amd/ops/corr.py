@@ -1,5 +1,6 @@
 """RAFT / GMA all-pairs correlation pyramid and window lookup (models/raft/corr.py:12-60 == models/gma/corr.py:15-63),
-also fused with convc1 + ReLU (update.py:79-93)."""
+also fused with convc1 + ReLU (update.py:79-93); and the same lookup computed on demand from the pooled features
+(OnDemandCorrBlock, models/raft/corr.py:63-91)."""
 import ctypes
 import os
 import weakref
@@ -227,6 +228,108 @@ class CorrBlock:
         st = self._state
         return [st.pyr[:, idx.to(st.pyr.device)].reshape(-1, 1, h, w)
                 for (idx, h, w) in tiled_index_maps(st.H, st.W, st.L)]
+
+
+# --------------------------------------------------------------------------- #
+# RAFT / GMA correlation on demand (Config.corr = "on_demand")
+# --------------------------------------------------------------------------- #
+class _OnDemandState:
+    """The build's workspace (include/pcfa_hip.h pcfa_corr_ondemand_*): features, pooled fmap2 pyramid, accumulators."""
+    __slots__ = ("B", "D", "H", "W", "L", "r", "ws", "token_grad", "accumulating")
+
+
+class _OnDemandBuild(torch.autograd.Function):
+    """fmap1, fmap2 -> 1-element token, as _CorrBuild: every lookup consumes the token, so this node's backward runs after
+    ALL lookup backwards have accumulated into the workspace and converts the sums once (pcfa_corr_ondemand_finish)."""
+
+    @staticmethod
+    def forward(ctx, fmap1, fmap2, state):
+        lib = _hip.load()
+        st = state
+        f1 = fmap1.contiguous()
+        f2 = fmap2.contiguous()
+        nbytes = int(lib.pcfa_corr_ondemand_workspace_bytes(st.B, st.D, st.H, st.W, st.L))
+        st.ws = torch.empty(nbytes, device=f1.device, dtype=torch.uint8)
+        _call("pcfa_corr_ondemand_prepare", _ptr(f1), _ptr(f2), _ptr(st.ws), st.B, st.D, st.H, st.W, st.L)
+        ctx.state = st
+        ctx.shape = f1.shape
+        return torch.zeros(1, device=f1.device, dtype=torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad_token):
+        st = ctx.state
+        if not st.accumulating:   # no lookup contributed a gradient
+            z = torch.zeros(ctx.shape, device=st.ws.device, dtype=torch.float32)
+            st.token_grad = None
+            return z, z.clone(), None
+        df1 = torch.empty(ctx.shape, device=st.ws.device, dtype=torch.float32)
+        df2 = torch.empty_like(df1)
+        _call("pcfa_corr_ondemand_finish", _ptr(st.ws), _ptr(df1), _ptr(df2), st.B, st.D, st.H, st.W, st.L)
+        st.accumulating = False
+        st.token_grad = None
+        return df1, df2, None
+
+
+class _OnDemandLookup(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, token, coords, state):
+        st = state
+        c = coords.contiguous()
+        n1 = 2 * st.r + 1
+        out = torch.empty((st.B, st.L * n1 * n1, st.H, st.W), device=c.device, dtype=torch.float32)
+        _call("pcfa_corr_ondemand_fwd", _ptr(st.ws), _ptr(c), _ptr(out), st.B, st.D, st.H, st.W, st.L, st.r)
+        ctx.state = st
+        ctx.save_for_backward(c)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        st = ctx.state
+        (c,) = ctx.saved_tensors
+        g = grad_out.contiguous()
+        _call("pcfa_corr_ondemand_bwd", _ptr(st.ws), _ptr(c), _ptr(g), int(st.accumulating), st.B, st.D, st.H, st.W,
+              st.L, st.r)
+        st.accumulating = True
+        return _token_grad(st, g.device), None, None
+
+
+class OnDemandCorrBlock:
+    """CorrBlock's constructor and __call__ without the all-pairs pyramid: every lookup computes its (2r+2)^2 window dot
+    products against the pooled fmap2 (the reference's AlternateCorrBlock, models/raft/corr.py:63-91).  Memory O(Q*D)
+    per build instead of O(Q^2); same values up to fp32 rounding; deterministic backward."""
+
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
+        _dev(fmap1, fmap2)
+        if fmap1.shape != fmap2.shape or fmap1.dim() != 4:
+            raise ValueError("OnDemandCorrBlock expects two [B,D,H,W] feature maps of equal shape")
+        lib = _hip.load()
+        self.num_levels = num_levels
+        self.radius = radius
+        st = _OnDemandState()
+        st.B, st.D, st.H, st.W = fmap1.shape
+        st.L, st.r = num_levels, radius
+        if (st.H >> (num_levels - 1)) < 1 or (st.W >> (num_levels - 1)) < 1:
+            raise ValueError("feature map %dx%d too small for %d pyramid levels" % (st.H, st.W, num_levels))
+        if lib.pcfa_corr_ondemand_workspace_bytes(st.B, st.D, st.H, st.W, num_levels) == 0 or not 1 <= radius <= 4:
+            raise ValueError("OnDemandCorrBlock: D=%d, %d levels, radius %d not served (D %% 4 == 0, D <= 512, radius 1..4)"
+                             % (st.D, num_levels, radius))
+        st.token_grad = None
+        st.accumulating = False
+        self._state = st
+        self._token = _OnDemandBuild.apply(fmap1, fmap2, st)
+
+    def __call__(self, coords):
+        _dev(coords)
+        if coords.requires_grad and torch.is_grad_enabled():
+            # checked here: inside Function.forward grad mode is off.  RAFT / GMA detach the coordinates
+            # (models/raft/raft.py:122-123); this operator has no gradient w.r.t. them
+            raise RuntimeError("OnDemandCorrBlock lookup: coords.requires_grad is not supported (detach the coordinates, "
+                               "as models/raft/raft.py:122-123 does)")
+        return _OnDemandLookup.apply(self._token, coords, self._state)
+
+    def lookup_conv_relu(self, coords, weight, bias, relu=True):
+        """No fused on-demand lookup -> convc1 kernel: the caller materialises the lookup."""
+        return None
 
 
 def tiled_index_maps(H, W, num_levels):

@@ -6,6 +6,7 @@ surrounding library work and can be captured into a hipGraph.
 
 Operator boundaries mirrored (reference file:line) -- one module per group:
   corr         CorrBlock                                      models/raft/corr.py:12-60 (== models/gma/corr.py:15-63)
+               OnDemandCorrBlock                              models/raft/corr.py:63-91 (AlternateCorrBlock)
   pwc          spatial_correlation_sample, pwc_cost_volume    .../spatial_correlation_sampler/spatial_correlation_sampler.py:9-91
                pwc_warp, deconv4s2_fewout, upsample_bilinear  models/PWCNet/PWCNet.py:166-206, :42-43, :73,321
   flownet      flownet_correlation, resample2d, channelnorm   models/FlowNet/{correlation,resample2d,channelnorm}_package/*.py
