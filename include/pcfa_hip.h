@@ -634,7 +634,8 @@ PCFA_API int pcfa_spynet_warp_bwd(const float* x, const float* flo, const float*
  * aligned, pcfa_conv7x7_packed_floats floats) holds the weight [Cout][Cin][7][7] in MFMA operand order: with
  * (mt, cot) = pcfa_conv7x7_tile(Cout), Cout padded to cot, Cin to 4 (zeros), the order is
  * [Cout / cot][Cin / 4][cot / mt][4 / (64 / mt)][7][7][64 / mt][mt] (packed on the host, ops.spynet.conv7x7_pack).
- * Fixed summation order, no atomics, no scratch: bitwise reproducible. */
+ * Fixed summation order, no atomics, no scratch: bitwise reproducible.  These three are the stride-1 / 7-tap instance of
+ * the pcfa_conv_gather kernel below (the same tile rule and operand order); ReLU and the addend exist on this entry only. */
 PCFA_API int pcfa_conv7x7_tile(int Cout, int* mt, int* cot);
 PCFA_API long long pcfa_conv7x7_packed_floats(int Cin, int Cout);
 PCFA_API int pcfa_conv7x7(const float* x, const float* mask, const float* packed, const float* bias, const float* addend,

@@ -109,6 +109,17 @@ __device__ __forceinline__ bool pcfa_xcd_item(const PcfaXcdMap& m, int lin, int&
   y = (k / m.a) * cy + yy;
   return x < m.gx && y < m.gy && yy < cy;
 }
+
+// maximum of m over a 256-thread workgroup, on every thread (red: 4 floats of LDS)
+__device__ __forceinline__ float block_max_256(float m, float* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+  __syncthreads();
+  m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __syncthreads();
+  return m;
+}
 #endif
 
 // ---- measurement hook -----------------------------------------------------------------------------------

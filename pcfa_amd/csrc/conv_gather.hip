@@ -1,11 +1,17 @@
-// FlowNet2's strided and transposed convolutions (reference models/FlowNet/submodules.py:7-36) and their data gradients on
-// the fp32 matrix cores of gfx950, for frozen weights (Config.flownet2_ops = "hip").
+// The direct convolutions of FlowNet2 (strided and transposed, reference models/FlowNet/submodules.py:7-36,
+// Config.flownet2_ops = "hip") and of SpyNet (7x7 / stride 1 / pad 3, models/SpyNet/SpyNet.py:56-84, Config.spynet_ops = "hip")
+// and their data gradients on the fp32 matrix cores of gfx950, for frozen weights.
 //
 // One kernel, two modes, both a direct implicit GEMM out[co][pixel] = sum_k Wp[co][k] . X[k][pixel] over
-// k = (input channel, ty, tx) with the layout of conv7x7.hip (output channels = MFMA rows, pixels = columns):
+// k = (input channel, ty, tx).  The OUTPUT CHANNELS are the A operand (MFMA rows), the PIXELS the B operand (columns): a
+// lane's accumulators are channels of ONE pixel, so every store instruction writes MT consecutive pixels of one channel
+// row.  MT = 32 (v_mfma_f32_32x32x2_f32, k pair = two input channels of one tap) for more than 16 output channels, MT = 16
+// (v_mfma_f32_16x16x4_f32, k quad) below, so a 16-row layer does not leave half of a 32-row tile idle.
 //   gather (npar = 1):  out[a][c] = sum W[ty][tx] x[S a + off + ty][S c + off + tx], S = 1 or 2, off = -pad.
-//                       Stride-2 k x k convolutions (k = 3, 5, 7) and the data gradient of ConvTranspose2d(4, 2, 1)
-//                       (a stride-2 4x4 convolution of grad_out with the deconvolution weight as it is).
+//                       Stride-2 k x k convolutions (k = 3, 5, 7), the data gradient of ConvTranspose2d(4, 2, 1)
+//                       (a stride-2 4x4 convolution of grad_out with the deconvolution weight as it is), and SpyNet's
+//                       7x7 layers (S = 1, pcfa_conv7x7; their data gradient is the same convolution of grad_out with
+//                       the 180-degree rotated, channel-transposed weight, ops.spynet.conv7x7_dgrad_weight).
 //   parity (npar = 4):  S = 1, output parity (ry, rx) = blockIdx.z % 4 owns the outputs (2 a + ry, 2 c + rx) and reads
 //                       x[a + off_ry + ty][c + off_rx + tx] with its own T x T sub-kernel.  A stride-2 transposed
 //                       convolution is exactly this: the forward of ConvTranspose2d(4, 2, 1) (T = 2) and the data
@@ -14,12 +20,15 @@
 // A workgroup (4 waves) owns PIX = TY x TX output pixels (TX = 64 for wide maps, 16 for the coarse ones) x COT output
 // channels; an MFMA column block is MT consecutive pixels of the tile in row-major order.  The K loop runs over chunks of
 // CK = 4 input channels, weights and the zero-padded input patch of the chunk staged in LDS, the next chunk requested into
-// registers before the current one is multiplied (as conv7x7.hip).  With S = 2 the patch rows are stored de-interleaved
-// (even columns, then odd columns), so the 32 lanes of a B read fall on consecutive LDS words.
+// registers before the current one is multiplied and written to LDS after it, so the global latency hides under the MFMAs.
+// Patch rows of one channel are padded so that the KS lane groups of an operand read (different channels, same tap) fall
+// on disjoint LDS banks.  With S = 2 the patch rows are stored de-interleaved (even columns, then odd columns), so the 32
+// lanes of a B read fall on consecutive LDS words.
 //
-// Epilogue: + bias, LeakyReLU(slope) when act == 2.  The data gradient applies the layer's LeakyReLU backward where grad_out
-// is loaded (mask = the layer's saved output: g where mask > 0, else g * mask_slope).  Every output element is one k-ordered
-// chain of MFMAs from zero, the same on every call: no split-K, no atomics, no scratch.
+// Epilogue: + bias, ReLU (act == 1) or LeakyReLU(slope) (act == 2), + addend.  The data gradient applies the layer's
+// activation backward where grad_out is loaded (mask = the layer's saved output: g where mask > 0, else g * mask_slope for
+// the LeakyReLU, a select of 0 for SpyNet's ReLU, so that a non-finite g under the mask contributes exactly 0).  Every output
+// element is one k-ordered chain of MFMAs from zero, the same on every call: no split-K, no atomics, no scratch.
 #include <type_traits>
 #include "common.hpp"
 
@@ -43,7 +52,10 @@ struct CgCfg {
   static constexpr int WFL = NBLK * STEPS * 64;          // packed weight floats per chunk
   static constexpr int R = (TY - 1) * S + T, CW = (TX - 1) * S + T;   // input patch rows / columns
   static constexpr int HALF = S == 2 ? (CW + 1) / 2 : CW;              // de-interleaved half row (S = 2)
-  static constexpr int RS = S == 2 ? 2 * HALF : CW;
+  // SpyNet's instance.  Its ReLU, addend and zero-select mask are compiled into this instance alone: as run-time branches
+  // of every instance they cost the stride-2 kernels 2-12 VGPRs and two of them a wave of occupancy (FlowNet2 -1 %).
+  static constexpr bool SPY = S == 1 && T == 7;
+  static constexpr int RS = S == 2 ? 2 * HALF : SPY ? 72 : CW;         // LDS row stride (SpyNet: 72, as it was measured)
   static constexpr int CHS = cg_pad_mod64(R * RS, MT);   // channel stride: the KS lane groups on disjoint banks
   static constexpr int PATCH = CG_CK * CHS;
   static constexpr int NTILE = PIX / MT, TPW = NTILE / 4;             // pixel tiles per workgroup / per wave
@@ -66,14 +78,15 @@ __device__ __forceinline__ AccT<C> mfma(float a, float b, const AccT<C>& acc) {
 
 struct CgArgs {
   const float* x;      // [B][Cin][H][W]
-  const float* mask;   // same shape or null: x * (mask > 0 ? 1 : mslope)
+  const float* mask;   // same shape or null: mask > 0 ? x : x * mslope (SpyNet's instance: mask > 0 ? x : 0)
   const float* wp;     // packed weights: [npar][Cout / cot][Cin / 4][cot / mt][4 / ks][T][T][ks][mt]
   const float* bias;   // [Cout] or null
+  const float* addend; // [B][Cout][OH][OW] or null, added after the activation (SpyNet's instance)
   float* out;          // [B][Cout][OH][OW]
   int Cin, H, W, Cout, OH, OW;
   int npar, off0, off1;   // gather: npar 1, off0 = -pad; parity: npar 4, off0 / off1 = input offset of parity 0 / 1
   int nchunk, ncot, tiles_x;
-  int act;                // 2: LeakyReLU(slope) after the bias
+  int act;                // after the bias: 1 ReLU (SpyNet's instance), 2 LeakyReLU(slope)
   float slope, mslope;
 };
 
@@ -84,7 +97,7 @@ __device__ __forceinline__ void cg_load(float4 (&rw)[C::NW4], float (&rp)[C::NP]
   const int tid = threadIdx.x;
   const float4* src = reinterpret_cast<const float4*>(wct + (size_t)ch * C::WFL);
 #pragma unroll
-  for (int i = 0; i < C::NW4; ++i)
+  for (int i = 0; i < C::NW4; ++i)   // (a clamped index here put rw in scratch memory)
     rw[i] = (i + 1 < C::NW4 || tid + CG_NT * i < C::WFL / 4) ? src[tid + CG_NT * i] : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
   for (int i = 0; i < C::NP; ++i) {
@@ -94,7 +107,7 @@ __device__ __forceinline__ void cg_load(float4 (&rw)[C::NW4], float (&rp)[C::NP]
     const bool ok = ci < Cin && iy >= 0 && iy < H && ix >= 0 && ix < W;
     const size_t off = (size_t)min(ci, Cin - 1) * plane + (size_t)min(max(iy, 0), H - 1) * W + min(max(ix, 0), W - 1);
     float v = xb[off];
-    if (mb) v = mb[off] > 0.f ? v : v * mslope;
+    if (mb) v = mb[off] > 0.f ? v : C::SPY ? 0.f : v * mslope;   // (a select: a non-finite v under the mask gives exactly 0)
     rp[i] = ok ? v : 0.f;
   }
 }
@@ -200,13 +213,16 @@ __global__ __launch_bounds__(CG_NT) void conv_gather_kernel(CgArgs a) {
         if (co >= a.Cout) continue;
         float v = acc[nb][t][r];
         if (a.bias) v += a.bias[co];
+        if (C::SPY && a.act == 1) v = v < 0.f ? 0.f : v;   // (NaN passes, as torch's relu)
         if (a.act == 2) v = v > 0.f ? v : v * a.slope;
-        a.out[((size_t)b * a.Cout + co) * a.OH * a.OW + pix] = v;
+        const size_t o = ((size_t)b * a.Cout + co) * a.OH * a.OW + pix;
+        if (C::SPY && a.addend) v += a.addend[o];
+        a.out[o] = v;
       }
   }
 }
 
-// (mt, cot, pixels per workgroup) by output channels, as conv7x7.hip
+// (mt, cot, pixels per workgroup) by output channels: 16 (<= 16 channels), 32, 64 (two 32-row blocks, half the pixels)
 int pick(int Cout) { return Cout <= 16 ? 16 : Cout <= 32 ? 32 : 64; }
 
 template <int S, int T, int TX>
@@ -230,7 +246,8 @@ int launch_tx(int p, CgArgs& a, int B, int OHl, int OWl, hipStream_t s) {
 template <int S, int T>
 int launch_st(CgArgs& a, int B, int OHl, int OWl, hipStream_t s) {
   const int p = pick(a.Cout);
-  return OWl >= 48 ? launch_tx<S, T, 64>(p, a, B, OHl, OWl, s) : launch_tx<S, T, 16>(p, a, B, OHl, OWl, s);
+  if constexpr (S == 1 && T == 7) return launch_tx<S, T, 64>(p, a, B, OHl, OWl, s);   // SpyNet: 64-pixel segments on every map
+  else return OWl >= 48 ? launch_tx<S, T, 64>(p, a, B, OHl, OWl, s) : launch_tx<S, T, 16>(p, a, B, OHl, OWl, s);
 }
 
 bool supported(int stride, int taps, int npar) {
@@ -264,8 +281,8 @@ extern "C" int pcfa_conv_gather(const float* x, const float* mask, float mask_sl
   if ((act != 0 && act != 2) || (reinterpret_cast<uintptr_t>(packed) & 15)) return PCFA_ERR_INVALID_ARG;
   if (!supported(stride, taps, npar)) return PCFA_ERR_UNSUPPORTED;
   if ((long long)B * npar > 65535) return PCFA_ERR_UNSUPPORTED;
-  CgArgs a{x, mask, packed, bias, out, Cin, H, W, Cout, OH, OW, npar, off0, off1, pcfa_cdiv(Cin, CG_CK), 0, 0, act, slope,
-           mask_slope};
+  CgArgs a{x, mask, packed, bias, nullptr, out, Cin, H, W, Cout, OH, OW, npar, off0, off1, pcfa_cdiv(Cin, CG_CK), 0, 0, act,
+           slope, mask_slope};
   const int OHl = npar == 4 ? (OH + 1) / 2 : OH, OWl = npar == 4 ? (OW + 1) / 2 : OW;   // parity 0: the largest
   hipStream_t s = (hipStream_t)stream;
   if (stride == 2) {
@@ -281,4 +298,18 @@ extern "C" int pcfa_conv_gather(const float* x, const float* mask, float mask_sl
     case 3: return launch_st<1, 3>(a, B, OHl, OWl, s);
     default: return launch_st<1, 4>(a, B, OHl, OWl, s);
   }
+}
+
+// SpyNet's 7x7 / stride 1 / pad 3 layers: the S = 1, T = 7 gather instance with ReLU (act 1) and the addend.
+extern "C" int pcfa_conv7x7_tile(int Cout, int* mt, int* cot) { return pcfa_conv_gather_tile(Cout, mt, cot); }
+
+extern "C" long long pcfa_conv7x7_packed_floats(int Cin, int Cout) { return pcfa_conv_gather_packed_floats(Cin, Cout, 7, 1); }
+
+extern "C" int pcfa_conv7x7(const float* x, const float* mask, const float* packed, const float* bias, const float* addend,
+                            float* out, int B, int Cin, int Cout, int H, int W, int relu, void* stream) {
+  if (!x || !packed || !out || B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1) return PCFA_ERR_INVALID_ARG;
+  if (reinterpret_cast<uintptr_t>(packed) & 15) return PCFA_ERR_INVALID_ARG;
+  CgArgs a{x, mask, packed, bias, addend, out, Cin, H, W, Cout, H, W, 1, -3, 0, pcfa_cdiv(Cin, CG_CK), 0, 0, relu ? 1 : 0,
+           0.f, 0.f};
+  return launch_st<1, 7>(a, B, H, W, (hipStream_t)stream);
 }

@@ -107,16 +107,6 @@ __device__ __forceinline__ Origin make_origin(float cx, float cy, int level, int
   return o;
 }
 
-__device__ __forceinline__ float block_max_256(float m, float* red) {   // 256 threads, result on every thread
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  __syncthreads();
-  return m;
-}
-
 // ---- prepare -----------------------------------------------------------------------------------------------------------
 // [B][D][Q] -> [B][Q][D] through a 32 x 33 LDS tile; block (32, 8), grid (cdiv(Q,32), cdiv(D,32), B)
 __global__ __launch_bounds__(256) void od_to_rows_kernel(const float* __restrict__ src, float* __restrict__ dst, int D,

@@ -235,16 +235,6 @@ constexpr int WARP_BMAX = 4096;   // block maxima of |grad_out| (one per block o
 // the non-finite pixels: a superset here, never finite garbage).
 constexpr int WARP_NONFINITE = -(1 << 20);
 
-__device__ __forceinline__ float block_max_256(float m, float* red) {   // 256 threads, result on every thread
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  __syncthreads();
-  return m;
-}
-
 // 2^shift = the fixed-point scale of this call (uniform over the grid: every block reduces the same block maxima)
 __device__ __forceinline__ int warp_fix_shift(const float* __restrict__ bmax, int nblk, float* red) {
   float m = 0.f;

@@ -3,36 +3,31 @@ conv3x3_cat, dense_block, conv_s2 (+ fused 1x1 downsample), conv_fewin, conv3x3_
 ReLU (models/raft/extractor.py, update.py; models/PWCNet/PWCNet.py:29-38,234-323; models/FlowNet/submodules.py)."""
 import ctypes
 import os
-import weakref
 
 import torch
 
 from .. import _hip
 from . import core
-from .core import _call, _dev, _ptr, _ptr_off, current_lane
-
-
-_sepconv_packs = {}  # id(weight) -> (weakref, version, fwd_packed, bwd_packed)
+from .core import _call, _dev, _ptr, _ptr_off, cached_pack, current_lane
 
 
 FEWIN_SHAPES = {(2, 7), (1, 7), (2, 5), (2, 3)}  # (Cin, ksize) instances of pcfa_conv_fewin_fwd
 _FEWIN_PACKED = os.environ.get("PCFA_FEWIN_PACKED", "1") != "0"   # A/B switch (tools/dev)
-_fewin_packs = {}  # id(weight) -> (weakref, version, packed)
+
+
+def _pack_cin_n_k(w, pack, packed_floats):
+    """One pack of an [N, Cin, k, k] weight by entry point `pack`(w, packed, Cin, N, k)."""
+    N, Cin, k, _ = w.shape
+    w = w.contiguous()
+    packed = torch.empty(int(getattr(_hip.load(), packed_floats)(Cin, N, k)), device=w.device, dtype=torch.float32)
+    _call(pack, _ptr(w), _ptr(packed), Cin, N, k)
+    return packed
 
 
 def _fewin_packed(weight):
     """pcfa_conv_fewin_pack of a frozen [N, Cin, k, k] weight (MFMA operand order), cached per tensor version."""
-    key = id(weight)
-    hit = _fewin_packs.get(key)
-    if hit is None or hit[0]() is not weight or hit[1] != weight._version:
-        lib = _hip.load()
-        N, Cin, k, _ = weight.shape
-        w = weight.detach().contiguous()
-        packed = torch.empty(int(lib.pcfa_conv_fewin_packed_floats(Cin, N, k)), device=w.device, dtype=torch.float32)
-        _call("pcfa_conv_fewin_pack", _ptr(w), _ptr(packed), Cin, N, k)
-        hit = (weakref.ref(weight, lambda _r, k_=key: _fewin_packs.pop(k_, None)), weight._version, packed)
-        _fewin_packs[key] = hit
-    return hit[2]
+    return cached_pack("fewin", (weight,),
+                       lambda w: _pack_cin_n_k(w, "pcfa_conv_fewin_pack", "pcfa_conv_fewin_packed_floats"))
 
 
 class _Conv1x1(torch.autograd.Function):
@@ -106,39 +101,15 @@ def conv_fewin(x, weight, bias=None, relu=False):
     return out
 
 
-_s2_packs = {}  # id(weight) -> (weakref, version, packed)
-
-
 def _s2_packed(weight):
     """pcfa_conv_s2_pack of a frozen [N, Cin, k, k] weight (MFMA operand order), cached per tensor version."""
-    key = id(weight)
-    hit = _s2_packs.get(key)
-    if hit is None or hit[0]() is not weight or hit[1] != weight._version:
-        lib = _hip.load()
-        N, Cin, k, _ = weight.shape
-        w = weight.detach().contiguous()
-        packed = torch.empty(int(lib.pcfa_conv_s2_packed_floats(Cin, N, k)), device=w.device, dtype=torch.float32)
-        _call("pcfa_conv_s2_pack", _ptr(w), _ptr(packed), Cin, N, k)
-        hit = (weakref.ref(weight, lambda _r, k_=key: _s2_packs.pop(k_, None)), weight._version, packed)
-        _s2_packs[key] = hit
-    return hit[2]
-
-
-_s2_bwd_packs = {}
+    return cached_pack("s2", (weight,), lambda w: _pack_cin_n_k(w, "pcfa_conv_s2_pack", "pcfa_conv_s2_packed_floats"))
 
 
 def _s2_bwd_packed(weight):
-    key = id(weight)
-    hit = _s2_bwd_packs.get(key)
-    if hit is None or hit[0]() is not weight or hit[1] != weight._version:
-        lib = _hip.load()
-        N, Cin, k, _ = weight.shape
-        w = weight.detach().contiguous()
-        packed = torch.empty(int(lib.pcfa_conv_s2_bwd_packed_floats(Cin, N, k)), device=w.device, dtype=torch.float32)
-        _call("pcfa_conv_s2_bwd_pack", _ptr(w), _ptr(packed), Cin, N, k)
-        hit = (weakref.ref(weight, lambda _r, k_=key: _s2_bwd_packs.pop(k_, None)), weight._version, packed)
-        _s2_bwd_packs[key] = hit
-    return hit[2]
+    """pcfa_conv_s2_bwd_pack of the same weight (the data gradient's operand order), cached per tensor version."""
+    return cached_pack("s2_bwd", (weight,),
+                       lambda w: _pack_cin_n_k(w, "pcfa_conv_s2_bwd_pack", "pcfa_conv_s2_bwd_packed_floats"))
 
 
 def conv_s2_supported(x, weight):
@@ -186,25 +157,18 @@ class _ConvS2(torch.autograd.Function):
         return gx, None, None, None, None, None, None
 
 
-_s2_ds_packs = {}   # (id(w), id(wd)) -> (weakref w, weakref wd, versions, fwd_packed, bwd_packed)
-
-
 def _s2_ds_packed(weight, weight_d):
-    key = (id(weight), id(weight_d))
-    hit = _s2_ds_packs.get(key)
-    ver = (weight._version, weight_d._version)
-    if hit is None or hit[0]() is not weight or hit[1]() is not weight_d or hit[2] != ver:
+    """(forward, data-gradient) packs of a 3x3 stride-2 weight and its 1x1 downsample, cached per version of both."""
+    def make(w, wd):
         lib = _hip.load()
-        N, Cin, _, _ = weight.shape
-        w, wd = weight.detach().contiguous(), weight_d.detach().contiguous()
+        N, Cin, _, _ = w.shape
+        w, wd = w.contiguous(), wd.contiguous()
         pf = torch.empty(int(lib.pcfa_conv_s2_ds_packed_floats(Cin, N)), device=w.device, dtype=torch.float32)
         pb = torch.empty(int(lib.pcfa_conv_s2_ds_bwd_packed_floats(Cin, N)), device=w.device, dtype=torch.float32)
         _call("pcfa_conv_s2_ds_pack", _ptr(w), _ptr(wd), _ptr(pf), Cin, N)
         _call("pcfa_conv_s2_ds_bwd_pack", _ptr(w), _ptr(wd), _ptr(pb), Cin, N)
-        drop = lambda _r, k_=key: _s2_ds_packs.pop(k_, None)
-        hit = (weakref.ref(weight, drop), weakref.ref(weight_d, drop), ver, pf, pb)
-        _s2_ds_packs[key] = hit
-    return hit[3], hit[4]
+        return pf, pb
+    return cached_pack("s2_ds", (weight, weight_d), make)
 
 
 def conv_s2_ds_supported(x, weight, weight_d):
@@ -399,18 +363,15 @@ def add_relu(a, b, b_is_relu=False):
 
 def _sepconv5_packed(weight):
     """pcfa_sepconv5_pack_weights of a frozen (1,5)/(5,1) Conv2d weight, cached per tensor version."""
-    key = id(weight)
-    hit = _sepconv_packs.get(key)
-    if hit is None or hit[0]() is not weight or hit[1] != weight._version:
-        cout, cin = weight.shape[:2]
-        w = weight.detach().contiguous()
+    def make(w):
+        cout, cin = w.shape[:2]
+        w = w.contiguous()
         lib = _hip.load()   # direct order + Winograd-domain weights (csrc/sepconv5_wino.hip)
         fwd = torch.empty(int(lib.pcfa_sepconv5_packed_floats(cout, cin)), device=w.device, dtype=torch.float32)
         bwd = torch.empty(int(lib.pcfa_sepconv5_packed_floats(cin, cout)), device=w.device, dtype=torch.float32)
         _call("pcfa_sepconv5_pack_weights", _ptr(w), _ptr(fwd), _ptr(bwd), cout, cin)
-        hit = (weakref.ref(weight, lambda _r, k=key: _sepconv_packs.pop(k, None)), weight._version, fwd, bwd)
-        _sepconv_packs[key] = hit
-    return hit[2], hit[3]
+        return fwd, bwd
+    return cached_pack("sepconv5", (weight,), make)
 
 
 class _SepConv5(torch.autograd.Function):
@@ -446,24 +407,18 @@ class _SepConv5(torch.autograd.Function):
         return gin[:, :Ca], (gin[:, Ca:] if Cb else None), None
 
 
-_conv3_packs = {}  # id(weight) -> (weakref, version, fwd_packed, bwd_packed)
-
-
 def _conv3x3_packed(weight):
     """pcfa_conv3x3_pack_weights of a frozen 3x3 Conv2d weight (Winograd-transformed, both directions), cached per
     tensor version."""
-    key = id(weight)
-    hit = _conv3_packs.get(key)
-    if hit is None or hit[0]() is not weight or hit[1] != weight._version:
-        cout, cin = weight.shape[:2]
+    def make(w):
+        cout, cin = w.shape[:2]
         lib = _hip.load()
-        w = weight.detach().contiguous()
+        w = w.contiguous()
         fwd = torch.empty(int(lib.pcfa_conv3x3_packed_floats(cin, cout)), device=w.device, dtype=torch.float32)
         bwd = torch.empty(int(lib.pcfa_conv3x3_packed_floats(cout, cin)), device=w.device, dtype=torch.float32)
         _call("pcfa_conv3x3_pack_weights", _ptr(w), _ptr(fwd), _ptr(bwd), cout, cin)
-        hit = (weakref.ref(weight, lambda _r, k=key: _conv3_packs.pop(k, None)), weight._version, fwd, bwd)
-        _conv3_packs[key] = hit
-    return hit[2], hit[3]
+        return fwd, bwd
+    return cached_pack("conv3x3", (weight,), make)
 
 
 _CONV_WS = {}   # device index -> scratch of pcfa_conv3x3_run (split-K partial outputs of the F(4x4,3x3) path)

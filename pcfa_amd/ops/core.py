@@ -3,6 +3,7 @@ the optional per-launch timers and the work recorder that bench.py's roofline ro
 import contextlib
 import ctypes
 import threading
+import weakref
 
 import torch
 
@@ -299,6 +300,23 @@ def _invoke(name, *args):
     else:
         status = fn(*args, _stream())
     _hip.check(status, name)
+
+
+_packs = {}   # (kind, id(weight), ...) -> (weakrefs, versions, what make() returned): every packed weight of the package
+
+
+def cached_pack(kind, weights, make):
+    """make(*detached weights) -- the pack, or a tuple of packs, of one or two frozen weight tensors in a kernel's operand
+    order -- cached per tensor version: built on first use (always an eager warm-up, before any capture), rebuilt when a
+    weight is written in place, dropped when a weight dies."""
+    key = (kind,) + tuple(id(w) for w in weights)
+    ver = tuple(w._version for w in weights)
+    hit = _packs.get(key)
+    if hit is None or hit[1] != ver or any(r() is not w for r, w in zip(hit[0], weights)):
+        drop = lambda _r, k=key: _packs.pop(k, None)   # noqa: E731
+        hit = (tuple(weakref.ref(w, drop) for w in weights), ver, make(*(w.detach() for w in weights)))
+        _packs[key] = hit
+    return hit[2]
 
 
 def work_recorder():

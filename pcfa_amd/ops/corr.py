@@ -3,13 +3,12 @@ also fused with convc1 + ReLU (update.py:79-93); and the same lookup computed on
 (OnDemandCorrBlock, models/raft/corr.py:63-91)."""
 import ctypes
 import os
-import weakref
 
 import torch
 
 from .. import _hip
 from . import core
-from .core import _call, _dev, _note_work, _pair, _ptr, _ptr_off, _stream
+from .core import _call, _dev, _note_work, _pair, _ptr, _ptr_off, _stream, cached_pack
 
 
 # --------------------------------------------------------------------------- #
@@ -130,22 +129,15 @@ class _CorrLookup(torch.autograd.Function):
         return _token_grad(st, g.device), None, None
 
 
-_convc1_packs = {}
-
-
 def _convc1_packed(weight):
     """pcfa_lookup_convc1_pack_weights of a frozen [256, 324, 1, 1] weight (both operand orders), cached per version."""
-    key = id(weight)
-    hit = _convc1_packs.get(key)
-    if hit is None or hit[0]() is not weight or hit[1] != weight._version:
-        lib = _hip.load()
-        cout = weight.shape[0]
-        w = weight.detach().reshape(cout, -1).contiguous()
-        packed = torch.empty(int(lib.pcfa_lookup_convc1_packed_floats(cout)), device=w.device, dtype=torch.float32)
+    def make(w):
+        cout = w.shape[0]
+        w = w.reshape(cout, -1).contiguous()
+        packed = torch.empty(int(_hip.load().pcfa_lookup_convc1_packed_floats(cout)), device=w.device, dtype=torch.float32)
         _call("pcfa_lookup_convc1_pack_weights", _ptr(w), _ptr(packed), cout, w.shape[1])
-        hit = (weakref.ref(weight, lambda _r, k=key: _convc1_packs.pop(k, None)), weight._version, packed)
-        _convc1_packs[key] = hit
-    return hit[2]
+        return packed
+    return cached_pack("convc1", (weight,), make)
 
 
 class _CorrLookupConv(torch.autograd.Function):

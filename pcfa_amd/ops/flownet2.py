@@ -8,21 +8,20 @@ The weight transforms are plain tensor ops (tested on the host in float64):
   parity_weights     a stride-2 transposed convolution as four stride-1 T x T sub-kernels, one per output parity;
   parity_offsets     the input offset of each parity's window.
 """
-import weakref
-
 import torch
 
 from .. import _hip
-from .core import _call, _dev, _ptr
+from .core import _call, _dev, _ptr, cached_pack
 
 __all__ = ["GATHER_CK", "gather_tile", "gather_pack", "parity_offsets", "parity_weights", "conv_s2_leaky",
            "deconv4s2_leaky", "resample2d_det", "upsample_nearest4", "leaky_relu", "conv_s2_leaky_covers"]
 
-GATHER_CK = 4   # input channels per chunk of pcfa_conv_gather (include/pcfa_hip.h)
+GATHER_CK = 4   # input channels per chunk of pcfa_conv_gather and pcfa_conv7x7 (include/pcfa_hip.h)
 
 
 def gather_tile(cout):
-    """(mt, cot) of pcfa_conv_gather for `cout` output channels (the library's rule, checked by _packs)."""
+    """(mt, cot) of pcfa_conv_gather / pcfa_conv7x7 for `cout` output channels: MFMA rows per tile and output channels per
+    workgroup (the library's rule, checked against it by ops.spynet)."""
     return (16, 16) if cout <= 16 else (32, 32) if cout <= 32 else (32, 64)
 
 
@@ -70,18 +69,6 @@ def parity_weights(w, pad):
     return out
 
 
-_packs = {}   # (kind, id(weight)) -> (weakref, version, packs)
-
-
-def _cached(kind, weight, make):
-    key = (kind, id(weight))
-    hit = _packs.get(key)
-    if hit is None or hit[0]() is not weight or hit[1] != weight._version:
-        hit = (weakref.ref(weight, lambda _r, k=key: _packs.pop(k, None)), weight._version, make(weight.detach().float()))
-        _packs[key] = hit
-    return hit[2]
-
-
 def _checked(packed, cin, cout, taps, npar):
     lib = _hip.load()
     if packed.numel() != int(lib.pcfa_conv_gather_packed_floats(cin, cout, taps, npar)):
@@ -120,7 +107,7 @@ class _ConvS2Leaky(torch.autograd.Function):
             _call("pcfa_conv_s2_fwd", _ptr(x), _ptr(_s2_packed(weight)), _ptr(bias), _ptr(out), B, cin, cout, H, W, k, 2,
                   float(slope))
         else:
-            fwd = _cached("s2f", weight, lambda w: _checked(gather_pack(w), cin, cout, k, 1))
+            fwd = cached_pack("s2f", (weight,), lambda w: _checked(gather_pack(w), cin, cout, k, 1))
             _gather(x, None, 0., fwd, bias, out, cin, cout, 2, k, 1, (-pad, 0), 2, slope)
         ctx.slope, ctx.xshape = float(slope), tuple(x.shape)
         ctx.save_for_backward(weight, out)
@@ -144,7 +131,8 @@ class _ConvS2Leaky(torch.autograd.Function):
             _call("pcfa_conv_s2_bwd", _ptr(gm), _ptr(_s2_bwd_packed(weight)), _ptr(gx), B, cin, cout, H, W, k)
         else:
             t = (k + 1) // 2
-            bwd = _cached("s2b", weight, lambda w: _checked(gather_pack(parity_weights(w, k // 2)), cout, cin, t, 4))
+            bwd = cached_pack("s2b", (weight,),
+                              lambda w: _checked(gather_pack(parity_weights(w, k // 2)), cout, cin, t, 4))
             _gather(g, out, ctx.slope, bwd, None, gx, cout, cin, 1, t, 4, parity_offsets(k, k // 2), 0, 0.)
         return gx, None, None, None
 
@@ -172,7 +160,7 @@ class _Deconv4s2Leaky(torch.autograd.Function):
         x = _aligned(x)
         B, cin, H, W = x.shape
         cout = int(weight.shape[1])
-        fwd = _cached("dcf", weight, lambda w: _checked(gather_pack(parity_weights(w, 1)), cin, cout, 2, 4))
+        fwd = cached_pack("dcf", (weight,), lambda w: _checked(gather_pack(parity_weights(w, 1)), cin, cout, 2, 4))
         out = torch.empty((B, cout, 2 * H, 2 * W), device=x.device, dtype=torch.float32)
         _gather(x, None, 0., fwd, bias, out, cin, cout, 1, 2, 4, parity_offsets(4, 1), 2, slope)
         ctx.slope, ctx.xshape = float(slope), tuple(x.shape)
@@ -189,7 +177,7 @@ class _Deconv4s2Leaky(torch.autograd.Function):
         cout = int(weight.shape[1])
         g = _aligned(g)
         # the data gradient of conv_transpose2d(., w, stride 2, padding 1) is conv2d(., w, stride 2, padding 1): w as it is
-        bwd = _cached("dcb", weight, lambda w: _checked(gather_pack(w), cout, cin, 4, 1))
+        bwd = cached_pack("dcb", (weight,), lambda w: _checked(gather_pack(w), cout, cin, 4, 1))
         gx = torch.empty(ctx.xshape, device=g.device, dtype=torch.float32)
         _gather(g, out, ctx.slope, bwd, None, gx, cout, cin, 2, 4, 1, (-1, 0), 0, 0.)
         return gx, None, None, None

@@ -2,23 +2,17 @@
 gradients, and the clamped backward warp (SpyNet.py:86-102) with a deterministic backward.  The flow up-sampling is
 ops.pwc.upsample_bilinear (gather backward)."""
 import ctypes
-import weakref
 
 import numpy as np
 import torch
 
 from .. import _hip
-from .core import _call, _dev, _ptr
+from .core import _call, _dev, _ptr, cached_pack
+from .flownet2 import gather_pack, gather_tile
 
 __all__ = ["conv7x7", "conv7x7_dgrad_weight", "conv7x7_pack", "conv7x7_tile", "spynet_warp", "spynet_warp_scales"]
 
-CONV7_CK = 4   # input channels per chunk of pcfa_conv7x7 (include/pcfa_hip.h)
-
-
-def conv7x7_tile(cout):
-    """(mt, cot) of pcfa_conv7x7 for `cout` output channels: MFMA rows per tile and output channels per workgroup.  The same
-    rule as the library's (checked against it by conv7x7_packed)."""
-    return (16, 16) if cout <= 16 else (32, 32) if cout <= 32 else (32, 64)
+conv7x7_tile = gather_tile   # pcfa_conv7x7 is the 7x7 / stride-1 instance of pcfa_conv_gather: one tile rule, one packer
 
 
 def conv7x7_dgrad_weight(w):
@@ -29,27 +23,15 @@ def conv7x7_dgrad_weight(w):
 
 def conv7x7_pack(w):
     """[Cout, Cin, 7, 7] -> pcfa_conv7x7's operand order (flat): [Cout/cot][Cin/4][cot/mt][4/ks][7][7][ks][mt], ks = 64/mt
-    k per MFMA step; Cout is padded to cot and Cin to 4 with zeros.  Plain tensor ops (host-testable)."""
-    cout, cin = int(w.shape[0]), int(w.shape[1])
-    mt, cot = conv7x7_tile(cout)
-    ks = 64 // mt
-    cop, cip = -(-cout // cot) * cot, -(-cin // CONV7_CK) * CONV7_CK
-    wp = w.new_zeros((cop, cip, 49))
-    wp[:cout, :cin] = w.reshape(cout, cin, 49)
-    wp = wp.view(cop // cot, cot // mt, mt, cip // CONV7_CK, CONV7_CK // ks, ks, 49)
-    return wp.permute(0, 3, 1, 4, 6, 5, 2).contiguous().view(-1)
-
-
-_conv7_packs = {}  # id(weight) -> (weakref, version, fwd_packed, dgrad_packed)
+    k per MFMA step; Cout is padded to cot and Cin to 4 with zeros (ops.flownet2.gather_pack of one 7x7 window)."""
+    return gather_pack(w)
 
 
 def _conv7_packed(weight):
-    """(forward, data-gradient) packs of a frozen 7x7 weight, cached per tensor version (the pattern of ops.conv)."""
-    key = id(weight)
-    hit = _conv7_packs.get(key)
-    if hit is None or hit[0]() is not weight or hit[1] != weight._version:
+    """(forward, data-gradient) packs of a frozen 7x7 weight, cached per tensor version."""
+    def make(w):
         lib = _hip.load()
-        w = weight.detach().float()
+        w = w.float()
         fwd, bwd = conv7x7_pack(w), conv7x7_pack(conv7x7_dgrad_weight(w))
         cout, cin = w.shape[:2]
         for p, (ci, co) in ((fwd, (cin, cout)), (bwd, (cout, cin))):
@@ -57,9 +39,8 @@ def _conv7_packed(weight):
             _hip.check(lib.pcfa_conv7x7_tile(co, ctypes.byref(mt), ctypes.byref(cot)), "pcfa_conv7x7_tile")
             if (mt.value, cot.value) != conv7x7_tile(co) or p.numel() != int(lib.pcfa_conv7x7_packed_floats(ci, co)):
                 raise RuntimeError("conv7x7: host packing does not match the library's tiling")
-        hit = (weakref.ref(weight, lambda _r, k=key: _conv7_packs.pop(k, None)), weight._version, fwd, bwd)
-        _conv7_packs[key] = hit
-    return hit[2], hit[3]
+        return fwd, bwd
+    return cached_pack("conv7x7", (weight,), make)
 
 
 class _Conv7x7(torch.autograd.Function):

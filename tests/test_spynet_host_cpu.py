@@ -82,3 +82,14 @@ def test_conv7x7_pack_layout(cin, cout):
                     assert float(p[idx]) == float(w[co, ci, ky, kx])
                     seen[idx] = True
     assert int((p != 0).sum()) == cout * cin * 49   # every weight once, zeros elsewhere
+
+
+@pytest.mark.parametrize("cin,cout", [(8, 32), (32, 64), (64, 32), (32, 16), (16, 2)])
+def test_conv7x7_pack_is_the_gather_pack(cin, cout):
+    """pcfa_conv7x7 is the 7x7 / stride-1 instance of pcfa_conv_gather: for every Basic layer, forward and data gradient,
+    the 7x7 packer and tile rule are the gather kernel's."""
+    from pcfa_amd.ops import flownet2
+    w = torch.randn(cout, cin, 7, 7, generator=torch.Generator().manual_seed(cin * 100 + cout))
+    for wk in (w, spy.conv7x7_dgrad_weight(w)):
+        assert spy.conv7x7_tile(wk.shape[0]) == flownet2.gather_tile(wk.shape[0])
+        assert torch.equal(spy.conv7x7_pack(wk), flownet2.gather_pack(wk))
