@@ -418,46 +418,9 @@ __global__ void resample2d_fwd_kernel(const float* __restrict__ in1, const float
 __global__ void resample2d_bwd_kernel(const float* __restrict__ in1, const float* __restrict__ flow,
                                       const float* __restrict__ gout, float* __restrict__ gin1,
                                       float* __restrict__ gflow, int B, int C, int iH, int iW, int H, int W) {
-  const long long total = (long long)B * H * W;
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  const int x = idx % W, y = (idx / W) % H, b = (int)(idx / ((long long)W * H));
-  const size_t plane = (size_t)H * W, iplane = (size_t)iH * iW;
-  const float dx = flow[((size_t)b * 2) * plane + (size_t)y * W + x];
-  const float dy = flow[((size_t)b * 2 + 1) * plane + (size_t)y * W + x];
-  const float xf = (float)x + dx, yf = (float)y + dy;
-  // grad_in1: neighbours clamped against the INPUT size, weights from truncation (xf - int(xf), :103-111)
-  const RsTaps t1 = rs_taps(xf, yf, iH, iW);
-  const float a1 = xf - (float)(int)xf, b1 = yf - (float)(int)yf;
-  // grad_flow: neighbours clamped against the flow size, gamma = 1 - frac (:159-170)
-  const RsTaps t2 = rs_taps(xf, yf, H, W);
-  const float gam_x = 1.f - t2.alpha, gam_y = 1.f - t2.beta;
-  const float* src = in1 + (size_t)b * C * iplane;
-  const float* g = gout + (size_t)b * C * plane + (size_t)y * W + x;
-  float* d1 = gin1 + (size_t)b * C * iplane;
-  float gdx = 0.f, gdy = 0.f;
-  for (int c = 0; c < C; ++c) {
-    const float gv = g[(size_t)c * plane];
-    float* d = d1 + (size_t)c * iplane;
-    unsafeAtomicAdd(d + (size_t)t1.yT * iW + t1.xL, (1.f - a1) * (1.f - b1) * gv);
-    unsafeAtomicAdd(d + (size_t)t1.yT * iW + t1.xR, a1 * (1.f - b1) * gv);
-    unsafeAtomicAdd(d + (size_t)t1.yB * iW + t1.xL, (1.f - a1) * b1 * gv);
-    unsafeAtomicAdd(d + (size_t)t1.yB * iW + t1.xR, a1 * b1 * gv);
-    const float* s = src + (size_t)c * iplane;
-    const float iTL = s[(size_t)t2.yT * iW + t2.xL], iTR = s[(size_t)t2.yT * iW + t2.xR];
-    const float iBL = s[(size_t)t2.yB * iW + t2.xL], iBR = s[(size_t)t2.yB * iW + t2.xR];
-    // channel 0 (d/dx): gamma from the y fraction; channel 1 (d/dy): gamma from the x fraction
-    gdx += gam_y * gv * iTR;
-    gdx -= gam_y * gv * iTL;
-    gdx += (1.f - gam_y) * gv * iBR;
-    gdx -= (1.f - gam_y) * gv * iBL;
-    gdy += gam_x * gv * iBL;
-    gdy -= gam_x * gv * iTL;
-    gdy += (1.f - gam_x) * gv * iBR;
-    gdy -= (1.f - gam_x) * gv * iTR;
-  }
-  gflow[((size_t)b * 2) * plane + (size_t)y * W + x] = gdx;
-  gflow[((size_t)b * 2 + 1) * plane + (size_t)y * W + x] = gdy;
+  if (idx >= (long long)B * H * W) return;
+  resample2d_bwd_pixel(in1, flow, gout, gflow, idx, C, iH, iW, H, W, [&](size_t i, float v) { unsafeAtomicAdd(gin1 + i, v); });
 }
 
 // ---------------------------------------------------------------------------------------------------------

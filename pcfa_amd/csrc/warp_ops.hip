@@ -8,7 +8,9 @@
 // which the library runs as ~14 launches forward (arange / repeat / cat / normalise, two grid_sampler_2d, compare,
 // cast, multiply) and two grid_sampler_2d_backward launches (221 us each at 32 x 96 x 320) plus elementwise
 // backward kernels.  Here: forward = one pass (read x where sampled, read flo, write out), backward = one pass that
-// scatters grad_x with hardware fp32 atomics (as grid_sampler_2d_backward does) and accumulates grad_flo.
+// scatters grad_x and accumulates grad_flo.  The scatter adds fixed-point int64 values (integer adds: the same bits on every
+// run; pwc_warp_bwd_det*_kernel, also SpyNet's warp and FlowNet2's Resample2d backward); hardware fp32 atomics, as
+// grid_sampler_2d_backward uses them, are the comparator behind Config.warp_bwd_deterministic = False (pwc_warp_bwd_kernel).
 // The coordinate arithmetic repeats the reference's fp32 operation sequence: normalise (x2, /(W-1), -1), then
 // grid_sample's un-normalisation ((g + 1) * W - 1) / 2 -- the two do NOT cancel (align_corners mismatch of the
 // original PWC-Net code), the sample position is x * W / (W - 1) - 0.5.
@@ -32,10 +34,13 @@ struct WarpTaps {
 };
 
 // Every kernel of this file (forward, fp32-atomic backward, the two fixed-point backward kernels) must form the same sample
-// position and the same flow-gradient sums BIT FOR BIT.  With contraction left to the optimiser, the same source expression
-// became an fma in one kernel and a multiply + add in another after an unrelated edit (r05: the non-finite flag), and the
-// "moves no bit" A/B of the two fixed-point kernels differed in the last place.  So the two shared pieces state their
-// roundings explicitly: no contraction inside them, an fma exactly where one is written.
+// position, the same weights and mask sum and the same flow-gradient sums BIT FOR BIT.  So that text exists once: warp_sample
+// below is the only prologue (position, taps, weights, validity, mask sum, offsets) and warp_scatter the only per-channel
+// backward body; a kernel adds its thread map, its mask decision and where an addend goes.  Inside them, what the optimiser
+// could still round differently per kernel states its roundings explicitly (warp_coord, tap_fma, mul_rounded, the SpyNet
+// grid: no contraction, an fma exactly where one is written) -- left to the optimiser, the same expression became an fma in
+// one kernel and a multiply + add in another after an unrelated edit (r05: the non-finite flag), and the "moves no bit" A/B
+// of the two fixed-point kernels differed in the last place.
 __device__ __forceinline__ float warp_coord(float base, float flow, int size) {
 #pragma clang fp contract(off)
   float g = 2.0f * (base + flow);
@@ -91,17 +96,72 @@ __device__ __forceinline__ float spy_unnormalize(float g, int size) {   // ((g +
   return fmaf(g + 1.f, (float)size, -1.f) / 2.f;
 }
 
-// sample position of pixel p: PWC-Net (SPY = false: meshgrid + fs * flo, normalised by W - 1) or SpyNet (SPY = true)
+// One pixel's sample: PWC-Net's position (SPY = false: meshgrid + fs * flo, normalised by W - 1) or SpyNet's (SPY = true),
+// its four taps with grid_sampler_2d's weights (nw = (ix_se - ix) * (iy_se - iy), ...), which taps lie inside the image, their
+// texel offsets in a plane (0 where outside, so that a load is always legal) and grid_sample(ones) = the in-bounds weights
+struct WarpSample {
+  WarpTaps t;
+  float ex, ey;              // ix_se - ix, iy_se - iy
+  float nw, ne, sw, se;
+  bool bnw, bne, bsw, bse;
+  int onw, one, osw, ose;
+  bool okx, oky;             // the SpyNet clamp passes the gradient (PWC-Net: always)
+  float msum;
+};
+
 template <bool SPY>
-__device__ __forceinline__ void sample_pos(const float* __restrict__ fb, long long p, long long plane, int px, int py, int H,
-                                           int W, float fs, const SpyGrid& sg, float& ix, float& iy, bool& okx, bool& oky) {
+__device__ __forceinline__ WarpSample warp_sample(const float* __restrict__ fb, long long p, long long plane, int px, int py,
+                                                  int H, int W, float fs, const SpyGrid& sg) {
+  WarpSample s;
+  float ix, iy;
   if constexpr (SPY) {
-    ix = spy_unnormalize(spy_grid(sg.hor[px], fb[p], sg.sx, &okx), W);
-    iy = spy_unnormalize(spy_grid(sg.ver[py], fb[plane + p], sg.sy, &oky), H);
+    ix = spy_unnormalize(spy_grid(sg.hor[px], fb[p], sg.sx, &s.okx), W);
+    iy = spy_unnormalize(spy_grid(sg.ver[py], fb[plane + p], sg.sy, &s.oky), H);
   } else {
     ix = warp_coord((float)px, mul_rounded(fb[p], fs), W);
     iy = warp_coord((float)py, mul_rounded(fb[plane + p], fs), H);
-    okx = oky = true;
+    s.okx = s.oky = true;
+  }
+  const WarpTaps t = s.t = warp_taps(ix, iy, H, W);
+  s.ex = (float)(t.x0 + 1) - ix, s.ey = (float)(t.y0 + 1) - iy;
+  s.nw = s.ex * s.ey, s.ne = t.wx1 * s.ey, s.sw = s.ex * t.wy1, s.se = t.wx1 * t.wy1;
+  s.bnw = t.vx0 && t.vy0, s.bne = t.vx1 && t.vy0, s.bsw = t.vx0 && t.vy1, s.bse = t.vx1 && t.vy1;
+  s.msum = 0.f;  // added in the kernels' tap order
+  if (s.bnw) s.msum += s.nw;
+  if (s.bne) s.msum += s.ne;
+  if (s.bsw) s.msum += s.sw;
+  if (s.bse) s.msum += s.se;
+  s.onw = s.bnw ? t.y0 * W + t.x0 : 0, s.one = s.bne ? t.y0 * W + t.x0 + 1 : 0;
+  s.osw = s.bsw ? (t.y0 + 1) * W + t.x0 : 0, s.ose = s.bse ? (t.y0 + 1) * W + t.x0 + 1 : 0;
+  return s;
+}
+
+// One channel of grid_sampler_2d_backward at one pixel: scatter w * g into x's gradient through put(tap, offset, addend),
+// gather the grid gradient from the in-bounds taps.  The four tap loads are unconditional (clamped offsets) so that they
+// are in flight together; only the adds are predicated.  Every addend is the plain fp32 product, formed before put sees it.
+template <class Put>
+__device__ __forceinline__ void warp_scatter(const WarpSample& s, const float* __restrict__ xc, float g, float& gix,
+                                             float& giy, Put put) {
+  const float vnw = xc[s.onw], vne = xc[s.one], vsw = xc[s.osw], vse = xc[s.ose];
+  if (s.bnw) {
+    put(0, s.onw, s.nw * g);
+    gix = tap_fma(gix, vnw, s.ey, g, true);
+    giy = tap_fma(giy, vnw, s.ex, g, true);
+  }
+  if (s.bne) {
+    put(1, s.one, s.ne * g);
+    gix = tap_fma(gix, vne, s.ey, g, false);
+    giy = tap_fma(giy, vne, s.t.wx1, g, true);
+  }
+  if (s.bsw) {
+    put(2, s.osw, s.sw * g);
+    gix = tap_fma(gix, vsw, s.t.wy1, g, true);
+    giy = tap_fma(giy, vsw, s.ex, g, false);
+  }
+  if (s.bse) {
+    put(3, s.ose, s.se * g);
+    gix = tap_fma(gix, vse, s.t.wy1, g, false);
+    giy = tap_fma(giy, vse, s.t.wx1, g, false);
   }
 }
 
@@ -114,34 +174,18 @@ __global__ __launch_bounds__(256) void pwc_warp_fwd_kernel(const float* __restri
   const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= plane) return;
   const int b = blockIdx.z, G = gridDim.y;
-  const int py = (int)(p / W), px = (int)(p % W);
-  const float* fb = flo + (size_t)b * 2 * plane;
-  float ix, iy;
-  bool okx, oky;
-  sample_pos<SPY>(fb, p, plane, px, py, H, W, fs, sg, ix, iy, okx, oky);
-  const WarpTaps t = warp_taps(ix, iy, H, W);
-  // weights as grid_sampler_2d forms them: nw = (ix_se - ix) * (iy_se - iy), ...
-  const float ex = (float)(t.x0 + 1) - ix, ey = (float)(t.y0 + 1) - iy;  // ix_se - ix, iy_se - iy
-  const float nw = ex * ey, ne = t.wx1 * ey, sw = ex * t.wy1, se = t.wx1 * t.wy1;
-  const bool bnw = t.vx0 && t.vy0, bne = t.vx1 && t.vy0, bsw = t.vx0 && t.vy1, bse = t.vx1 && t.vy1;
-  float msum = 0.f;  // grid_sample(ones): the in-bounds weights, added in the kernel's tap order
-  if (bnw) msum += nw;
-  if (bne) msum += ne;
-  if (bsw) msum += sw;
-  if (bse) msum += se;
-  const float m = msum >= mask_thresh ? 1.f : 0.f;
-  const int onw = bnw ? t.y0 * W + t.x0 : 0, one = bne ? t.y0 * W + t.x0 + 1 : 0;
-  const int osw = bsw ? (t.y0 + 1) * W + t.x0 : 0, ose = bse ? (t.y0 + 1) * W + t.x0 + 1 : 0;
+  const WarpSample s = warp_sample<SPY>(flo + (size_t)b * 2 * plane, p, plane, (int)(p % W), (int)(p / W), H, W, fs, sg);
+  const float m = s.msum >= mask_thresh ? 1.f : 0.f;
   const float* xb = x + (size_t)b * C * plane;
   float* ob = out + (size_t)b * C * plane + p;
   for (int c = blockIdx.y; c < C; c += G) {
     const float* xc = xb + (size_t)c * plane;
     float v = 0.f;
-    const float a = xc[onw], bq = xc[one], cq = xc[osw], d = xc[ose];
-    if (bnw) v += a * nw;
-    if (bne) v += bq * ne;
-    if (bsw) v += cq * sw;
-    if (bse) v += d * se;
+    const float a = xc[s.onw], bq = xc[s.one], cq = xc[s.osw], d = xc[s.ose];
+    if (s.bnw) v += a * s.nw;
+    if (s.bne) v += bq * s.ne;
+    if (s.bsw) v += cq * s.sw;
+    if (s.bse) v += d * s.se;
     ob[(size_t)c * plane] = v * m;
   }
 }
@@ -151,60 +195,20 @@ __global__ __launch_bounds__(256) void pwc_warp_bwd_kernel(const float* __restri
                                                           const float* __restrict__ gout, float* __restrict__ gx,
                                                           float* __restrict__ gflo, int C, int H, int W,
                                                           float mask_thresh, float fs) {
-  constexpr bool SPY = false;
-  const SpyGrid sg{};
   const long long plane = (long long)H * W;
   const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= plane) return;
   const int b = blockIdx.z, G = gridDim.y;
-  const int py = (int)(p / W), px = (int)(p % W);
-  const float* fb = flo + (size_t)b * 2 * plane;
-  float ix, iy;
-  bool okx, oky;
-  sample_pos<SPY>(fb, p, plane, px, py, H, W, fs, sg, ix, iy, okx, oky);
-  const WarpTaps t = warp_taps(ix, iy, H, W);
-  const float ex = (float)(t.x0 + 1) - ix, ey = (float)(t.y0 + 1) - iy;
-  const float nw = ex * ey, ne = t.wx1 * ey, sw = ex * t.wy1, se = t.wx1 * t.wy1;
-  const bool bnw = t.vx0 && t.vy0, bne = t.vx1 && t.vy0, bsw = t.vx0 && t.vy1, bse = t.vx1 && t.vy1;
-  float msum = 0.f;
-  if (bnw) msum += nw;
-  if (bne) msum += ne;
-  if (bsw) msum += sw;
-  if (bse) msum += se;
-  if (!(msum >= mask_thresh)) return;  // output * 0: no gradient to either input (buffers are zero)
-  const int onw = bnw ? t.y0 * W + t.x0 : 0, one = bne ? t.y0 * W + t.x0 + 1 : 0;
-  const int osw = bsw ? (t.y0 + 1) * W + t.x0 : 0, ose = bse ? (t.y0 + 1) * W + t.x0 + 1 : 0;
+  const WarpSample s = warp_sample<false>(flo + (size_t)b * 2 * plane, p, plane, (int)(p % W), (int)(p / W), H, W, fs, SpyGrid{});
+  if (!(s.msum >= mask_thresh)) return;  // output * 0: no gradient to either input (buffers are zero)
   const float* xb = x + (size_t)b * C * plane;
   float* gb = gx + (size_t)b * C * plane;
   const float* go = gout + (size_t)b * C * plane + p;
   float gix = 0.f, giy = 0.f;
   for (int c = blockIdx.y; c < C; c += G) {
-    const float g = go[(size_t)c * plane];
-    const float* xc = xb + (size_t)c * plane;
     float* gc = gb + (size_t)c * plane;
-    // grid_sampler_2d_backward: scatter into x, gather the grid gradient from the in-bounds taps.  The four tap
-    // loads are unconditional (clamped offsets) so that they are in flight together; only the atomics are predicated.
-    const float vnw = xc[onw], vne = xc[one], vsw = xc[osw], vse = xc[ose];
-    if (bnw) {
-      unsafeAtomicAdd(gc + onw, nw * g);
-      gix = tap_fma(gix, vnw, ey, g, true);
-      giy = tap_fma(giy, vnw, ex, g, true);
-    }
-    if (bne) {
-      unsafeAtomicAdd(gc + one, ne * g);
-      gix = tap_fma(gix, vne, ey, g, false);
-      giy = tap_fma(giy, vne, t.wx1, g, true);
-    }
-    if (bsw) {
-      unsafeAtomicAdd(gc + osw, sw * g);
-      gix = tap_fma(gix, vsw, t.wy1, g, true);
-      giy = tap_fma(giy, vsw, ex, g, false);
-    }
-    if (bse) {
-      unsafeAtomicAdd(gc + ose, se * g);
-      gix = tap_fma(gix, vse, t.wy1, g, false);
-      giy = tap_fma(giy, vse, t.wx1, g, false);
-    }
+    warp_scatter(s, xb + (size_t)c * plane, go[(size_t)c * plane], gix, giy,
+                 [&](int, int o, float v) { unsafeAtomicAdd(gc + o, v); });
   }
   // d ix / d grid = W / 2 (unnormalize), d grid / d flo = 2 / max(W - 1, 1) (the reference divides, then doubles)
   const float dfx = mul_rounded(2.0f * ((0.5f * (float)W * gix) / (float)max(W - 1, 1)), fs);   // d (fs flo) / d flo
@@ -269,60 +273,24 @@ __global__ __launch_bounds__(256) void pwc_warp_bwd_det_kernel(const float* __re
   const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= plane) return;
   const int b = blockIdx.z, G = gridDim.y, B = gridDim.z;
-  const int py = (int)(p / W), px = (int)(p % W);
-  const float* fb = flo + (size_t)b * 2 * plane;
   float* gf = gfpart + ((size_t)blockIdx.y * B + b) * 2 * plane;   // this channel group's partial flow gradient
-  float ix, iy;
-  bool okx, oky;
-  sample_pos<SPY>(fb, p, plane, px, py, H, W, fs, sg, ix, iy, okx, oky);
-  const WarpTaps t = warp_taps(ix, iy, H, W);
-  const float ex = (float)(t.x0 + 1) - ix, ey = (float)(t.y0 + 1) - iy;
-  const float nw = ex * ey, ne = t.wx1 * ey, sw = ex * t.wy1, se = t.wx1 * t.wy1;
-  const bool bnw = t.vx0 && t.vy0, bne = t.vx1 && t.vy0, bsw = t.vx0 && t.vy1, bse = t.vx1 && t.vy1;
-  float msum = 0.f;
-  if (bnw) msum += nw;
-  if (bne) msum += ne;
-  if (bsw) msum += sw;
-  if (bse) msum += se;
-  if (!(msum >= mask_thresh)) {   // output * 0: no gradient to either input
+  const WarpSample s = warp_sample<SPY>(flo + (size_t)b * 2 * plane, p, plane, (int)(p % W), (int)(p / W), H, W, fs, sg);
+  if (!(s.msum >= mask_thresh)) {   // output * 0: no gradient to either input
     gf[p] = 0.f;
     gf[plane + p] = 0.f;
     return;
   }
-  const int onw = bnw ? t.y0 * W + t.x0 : 0, one = bne ? t.y0 * W + t.x0 + 1 : 0;
-  const int osw = bsw ? (t.y0 + 1) * W + t.x0 : 0, ose = bse ? (t.y0 + 1) * W + t.x0 + 1 : 0;
   const float* xb = x + (size_t)b * C * plane;
   long long* gb = gxi + (size_t)b * C * plane;
   const float* go = gout + (size_t)b * C * plane + p;
   float gix = 0.f, giy = 0.f;
   for (int c = blockIdx.y; c < C; c += G) {
-    const float g = go[(size_t)c * plane];
-    const float* xc = xb + (size_t)c * plane;
     long long* gc = gb + (size_t)c * plane;
-    const float vnw = xc[onw], vne = xc[one], vsw = xc[osw], vse = xc[ose];
-    if (bnw) {
-      fix_add(gc + onw, nw * g, scale);
-      gix = tap_fma(gix, vnw, ey, g, true);
-      giy = tap_fma(giy, vnw, ex, g, true);
-    }
-    if (bne) {
-      fix_add(gc + one, ne * g, scale);
-      gix = tap_fma(gix, vne, ey, g, false);
-      giy = tap_fma(giy, vne, t.wx1, g, true);
-    }
-    if (bsw) {
-      fix_add(gc + osw, sw * g, scale);
-      gix = tap_fma(gix, vsw, t.wy1, g, true);
-      giy = tap_fma(giy, vsw, ex, g, false);
-    }
-    if (bse) {
-      fix_add(gc + ose, se * g, scale);
-      gix = tap_fma(gix, vse, t.wy1, g, false);
-      giy = tap_fma(giy, vse, t.wx1, g, false);
-    }
+    warp_scatter(s, xb + (size_t)c * plane, go[(size_t)c * plane], gix, giy,
+                 [&](int, int o, float v) { fix_add(gc + o, v, scale); });
   }
-  gf[p] = flow_grad<SPY>(gix, W, okx);
-  gf[plane + p] = flow_grad<SPY>(giy, H, oky);
+  gf[p] = flow_grad<SPY>(gix, W, s.okx);
+  gf[plane + p] = flow_grad<SPY>(giy, H, s.oky);
 }
 
 // The same scatter through an LDS window.  The cost of the kernel above is its global atomics, and an atomic instruction
@@ -350,21 +318,10 @@ __global__ __launch_bounds__(256) void pwc_warp_bwd_det_lds_kernel(
   const int py = min(py0, H - 1), px = min(px0, W - 1);
   const long long p = (long long)py * W + px;
   const int b = blockIdx.z, G = gridDim.y, B = gridDim.z;
-  const float* fb = flo + (size_t)b * 2 * plane;
   float* gf = gfpart + ((size_t)blockIdx.y * B + b) * 2 * plane;
-  float ix, iy;
-  bool okx, oky;
-  sample_pos<SPY>(fb, p, plane, px, py, H, W, fs, sg, ix, iy, okx, oky);
-  const WarpTaps t = warp_taps(ix, iy, H, W);
-  const float ex = (float)(t.x0 + 1) - ix, ey = (float)(t.y0 + 1) - iy;
-  const float nw = ex * ey, ne = t.wx1 * ey, sw = ex * t.wy1, se = t.wx1 * t.wy1;
-  const bool bnw = t.vx0 && t.vy0, bne = t.vx1 && t.vy0, bsw = t.vx0 && t.vy1, bse = t.vx1 && t.vy1;
-  float msum = 0.f;
-  if (bnw) msum += nw;
-  if (bne) msum += ne;
-  if (bsw) msum += sw;
-  if (bse) msum += se;
-  const bool act = inside && msum >= mask_thresh;   // else output * 0: no gradient to either input
+  const WarpSample s = warp_sample<SPY>(flo + (size_t)b * 2 * plane, p, plane, px, py, H, W, fs, sg);
+  const WarpTaps& t = s.t;
+  const bool act = inside && s.msum >= mask_thresh;   // else output * 0: no gradient to either input
   if (tid == (WT / 2) * WT + WT / 2) {   // window origin: the centre pixel's target, centred (clamped so that the window
     s_org[0] = min(max(t.y0 - (WWIN - WT) / 2 - WT / 2 + 1, -1), max(H - WWIN + 1, -1));   // overlaps the image where it can)
     s_org[1] = min(max(t.x0 - (WWIN - WT) / 2 - WT / 2 + 1, -1), max(W - WWIN + 1, -1));
@@ -376,48 +333,23 @@ __global__ __launch_bounds__(256) void pwc_warp_bwd_det_lds_kernel(
   const int ly = t.y0 - wy0, lx = t.x0 - wx0;
   const bool iny0 = ly >= 0 && ly < WWIN, iny1 = ly + 1 >= 0 && ly + 1 < WWIN;
   const bool inx0 = lx >= 0 && lx < WWIN, inx1 = lx + 1 >= 0 && lx + 1 < WWIN;
-  const int cnw = (iny0 && inx0) ? ly * WWIN + lx : -1, cne = (iny0 && inx1) ? ly * WWIN + lx + 1 : -1;
-  const int csw = (iny1 && inx0) ? (ly + 1) * WWIN + lx : -1, cse = (iny1 && inx1) ? (ly + 1) * WWIN + lx + 1 : -1;
-  const int onw = bnw ? t.y0 * W + t.x0 : 0, one = bne ? t.y0 * W + t.x0 + 1 : 0;
-  const int osw = bsw ? (t.y0 + 1) * W + t.x0 : 0, ose = bse ? (t.y0 + 1) * W + t.x0 + 1 : 0;
+  const int cell[4] = {(iny0 && inx0) ? ly * WWIN + lx : -1, (iny0 && inx1) ? ly * WWIN + lx + 1 : -1,               // nw, ne
+                       (iny1 && inx0) ? (ly + 1) * WWIN + lx : -1, (iny1 && inx1) ? (ly + 1) * WWIN + lx + 1 : -1};  // sw, se
   const float* xb = x + (size_t)b * C * plane;
   long long* gb = gxi + (size_t)b * C * plane;
   const float* go = gout + (size_t)b * C * plane + p;
   float gix = 0.f, giy = 0.f;
-  auto put = [&](int j, int cell, long long* gaddr, float v) {
-    const unsigned long long q = (unsigned long long)__double2ll_rn((double)v * scale);
-    if (cell >= 0) atomicAdd(&win[j][cell], q);
-    else atomicAdd(reinterpret_cast<unsigned long long*>(gaddr), q);
-  };
   for (int c0 = blockIdx.y; c0 < C; c0 += G * WCH) {   // (workgroup-uniform trip count: barriers inside)
 #pragma unroll
     for (int j = 0; j < WCH; ++j) {
       const int c = c0 + j * G;
       if (c < C && act) {
-        const float g = go[(size_t)c * plane];
-        const float* xc = xb + (size_t)c * plane;
         long long* gc = gb + (size_t)c * plane;
-        const float vnw = xc[onw], vne = xc[one], vsw = xc[osw], vse = xc[ose];
-        if (bnw) {
-          put(j, cnw, gc + onw, nw * g);
-          gix = tap_fma(gix, vnw, ey, g, true);
-          giy = tap_fma(giy, vnw, ex, g, true);
-        }
-        if (bne) {
-          put(j, cne, gc + one, ne * g);
-          gix = tap_fma(gix, vne, ey, g, false);
-          giy = tap_fma(giy, vne, t.wx1, g, true);
-        }
-        if (bsw) {
-          put(j, csw, gc + osw, sw * g);
-          gix = tap_fma(gix, vsw, t.wy1, g, true);
-          giy = tap_fma(giy, vsw, ex, g, false);
-        }
-        if (bse) {
-          put(j, cse, gc + ose, se * g);
-          gix = tap_fma(gix, vse, t.wy1, g, false);
-          giy = tap_fma(giy, vse, t.wx1, g, false);
-        }
+        warp_scatter(s, xb + (size_t)c * plane, go[(size_t)c * plane], gix, giy, [&](int tap, int o, float v) {
+          const unsigned long long q = (unsigned long long)__double2ll_rn((double)v * scale);
+          if (cell[tap] >= 0) atomicAdd(&win[j][cell[tap]], q);
+          else atomicAdd(reinterpret_cast<unsigned long long*>(gc + o), q);
+        });
       }
     }
     __syncthreads();
@@ -434,8 +366,8 @@ __global__ __launch_bounds__(256) void pwc_warp_bwd_det_lds_kernel(
     __syncthreads();
   }
   if (inside) {
-    gf[p] = act ? flow_grad<SPY>(gix, W, okx) : 0.f;
-    gf[plane + p] = act ? flow_grad<SPY>(giy, H, oky) : 0.f;
+    gf[p] = act ? flow_grad<SPY>(gix, W, s.okx) : 0.f;
+    gf[plane + p] = act ? flow_grad<SPY>(giy, H, s.oky) : 0.f;
   }
 }
 
@@ -514,7 +446,27 @@ size_t warp_bwd_det_workspace_bytes(int B, int C, int H, int W) {
          WARP_BMAX * sizeof(float);
 }
 
-// {clear + max, fixed-point scatter + flow-gradient partials, finish}; flow_scale / fsy: the finish's factor along x / y
+// The fixed-point scatter's host sequence over workspace = {nx int64 accumulators, G * nf flow-gradient partials, WARP_BMAX
+// block maxima}: clear + block maxima of |grad_out|, scatter(gxi, gfpart, bmax, nblk) (one launch), finish (grad_x = sums *
+// unit; grad_flo = the G partials added in index order, times fs along x / fsy along y; plane = pixels per flow channel)
+template <class Scatter>
+int fixed_point_scatter(void* workspace, long long nx, const float* grad_out, Scatter scatter, float* grad_x, float* grad_flo,
+                        long long nf, int G, float fs, float fsy, long long plane, hipStream_t s) {
+  long long* gxi = (long long*)workspace;
+  float* gfpart = (float*)(gxi + nx);
+  float* bmax = gfpart + (size_t)G * nf;
+  const int nblk = (int)min((nx + 255) / 256, (long long)WARP_BMAX);
+  pcfa_launch(zero_ll_max_kernel, dim3(nblk), dim3(256), 0, s, gxi, grad_out, bmax, nx);
+  PCFA_LAUNCH_CHECK();
+  scatter(gxi, gfpart, (const float*)bmax, nblk);
+  PCFA_LAUNCH_CHECK();
+  pcfa_launch(pwc_warp_finish_kernel, dim3((int)min((nx + nf + 255) / 256, 4096LL)), dim3(256), 0, s,
+              (const long long*)gxi, (const float*)gfpart, (const float*)bmax, nblk, grad_x, grad_flo, nx, nf, G, fs, fsy, plane);
+  PCFA_LAUNCH_CHECK();
+  return PCFA_OK;
+}
+
+// flow_scale / fsy: the finish's factor along x / y
 template <bool SPY>
 int warp_bwd_det(const float* x, const float* flo, const float* grad_out, float* grad_x, float* grad_flo, void* workspace,
                  size_t workspace_bytes, int B, int C, int H, int W, float mask_threshold, float flow_scale, float fsy,
@@ -522,82 +474,37 @@ int warp_bwd_det(const float* x, const float* flo, const float* grad_out, float*
   if (workspace_bytes < warp_bwd_det_workspace_bytes(B, C, H, W)) return PCFA_ERR_WORKSPACE;
   if (reinterpret_cast<uintptr_t>(workspace) & 7) return PCFA_ERR_INVALID_ARG;
   const long long plane = (long long)H * W;
-  const long long nx = (long long)B * C * plane, nf = (long long)B * 2 * plane;
   const int G = channel_groups(plane, C);
-  long long* gxi = (long long*)workspace;
-  float* gfpart = (float*)(gxi + nx);
-  float* bmax = gfpart + (size_t)G * nf;
-  const int nblk = (int)min((nx + 255) / 256, (long long)WARP_BMAX);
-  pcfa_launch(zero_ll_max_kernel, dim3(nblk), dim3(256), 0, s, gxi, grad_out, bmax, nx);
-  PCFA_LAUNCH_CHECK();
-  // PCFA_WARP_SCATTER=global: one global atomic per tap (the r03 kernel; dev A/B, read once)
-  static const bool lds_window = !(getenv("PCFA_WARP_SCATTER") && getenv("PCFA_WARP_SCATTER")[0] == 'g');
-  if (lds_window && plane >= 256) {   // (tiny planes: the window's clear / flush passes cost more than they save)
-    const int tiles_x = pcfa_cdiv(W, WT), tiles_y = pcfa_cdiv(H, WT);
-    dim3 grid((unsigned)(tiles_x * tiles_y), G, B);
-    pcfa_launch(pwc_warp_bwd_det_lds_kernel<SPY>, grid, dim3(256), 0, s, x, flo, grad_out, gxi, gfpart, (const float*)bmax,
-                nblk, C, H, W, mask_threshold, flow_scale, tiles_x, sg);
-  } else {
-    dim3 grid(pcfa_cdiv(plane, 256), G, B);
-    pcfa_launch(pwc_warp_bwd_det_kernel<SPY>, grid, dim3(256), 0, s, x, flo, grad_out, gxi, gfpart, (const float*)bmax, nblk,
-                C, H, W, mask_threshold, flow_scale, sg);
-  }
-  PCFA_LAUNCH_CHECK();
-  pcfa_launch(pwc_warp_finish_kernel, dim3((int)min((nx + nf + 255) / 256, 4096LL)), dim3(256), 0, s,
-              (const long long*)gxi, (const float*)gfpart, (const float*)bmax, nblk, grad_x, grad_flo, nx, nf, G, flow_scale,
-              fsy, plane);
-  PCFA_LAUNCH_CHECK();
-  return PCFA_OK;
+  auto scatter = [&](long long* gxi, float* gfpart, const float* bmax, int nblk) {
+    // PCFA_WARP_SCATTER=global: one global atomic per tap (the r03 kernel; dev A/B, read once)
+    static const bool lds_window = !(getenv("PCFA_WARP_SCATTER") && getenv("PCFA_WARP_SCATTER")[0] == 'g');
+    if (lds_window && plane >= 256) {   // (tiny planes: the window's clear / flush passes cost more than they save)
+      const int tiles_x = pcfa_cdiv(W, WT), tiles_y = pcfa_cdiv(H, WT);
+      dim3 grid((unsigned)(tiles_x * tiles_y), G, B);
+      pcfa_launch(pwc_warp_bwd_det_lds_kernel<SPY>, grid, dim3(256), 0, s, x, flo, grad_out, gxi, gfpart, bmax, nblk, C, H, W,
+                  mask_threshold, flow_scale, tiles_x, sg);
+    } else {
+      dim3 grid(pcfa_cdiv(plane, 256), G, B);
+      pcfa_launch(pwc_warp_bwd_det_kernel<SPY>, grid, dim3(256), 0, s, x, flo, grad_out, gxi, gfpart, bmax, nblk, C, H, W,
+                  mask_threshold, flow_scale, sg);
+    }
+  };
+  return fixed_point_scatter(workspace, (long long)B * C * plane, grad_out, scatter, grad_x, grad_flo, (long long)B * 2 * plane,
+                             G, flow_scale, fsy, plane, s);
 }
 
 // FlowNet2's Resample2d backward (resample2d_kernel.cu:75-201) with grad_in1 through the fixed-point scatter above instead
-// of fp32 atomics: one thread per output pixel, the reference's coordinates (x + flow_x, y + flow_y), neighbours clamped
-// against the input size, truncation weights (xf - int(xf)), each addend the same fp32 product as the atomic kernel of
-// flownet_ops.hip forms, rounded once to the call's fixed-point unit.  The flow gradient is the reference's gather, written
-// directly (one thread owns every channel of its pixel).  in1 has the flow's size (FlowNet2 warps full-size images).
+// of fp32 atomics: the per-pixel body of the atomic kernel of flownet_ops.hip (resample2d_taps.hpp), each addend rounded
+// once to the call's fixed-point unit.  in1 has the flow's size (FlowNet2 warps full-size images): iH = H, iW = W.
 __global__ __launch_bounds__(256) void resample2d_bwd_det_kernel(const float* __restrict__ in1, const float* __restrict__ flow,
                                                                 const float* __restrict__ gout, long long* __restrict__ gxi,
                                                                 float* __restrict__ gflow, const float* __restrict__ bmax,
                                                                 int nblk, int B, int C, int H, int W) {
   __shared__ float red[4];
   const double scale = ldexp(1.0, warp_fix_shift(bmax, nblk, red));   // (block-wide: before any thread leaves)
-  const long long total = (long long)B * H * W;
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  const int x = idx % W, y = (idx / W) % H, b = (int)(idx / ((long long)W * H));
-  const size_t plane = (size_t)H * W;
-  const float dx = flow[((size_t)b * 2) * plane + (size_t)y * W + x];
-  const float dy = flow[((size_t)b * 2 + 1) * plane + (size_t)y * W + x];
-  const float xf = (float)x + dx, yf = (float)y + dy;
-  const RsTaps t1 = rs_taps(xf, yf, H, W);
-  const float a1 = xf - (float)(int)xf, b1 = yf - (float)(int)yf;
-  const RsTaps& t2 = t1;   // the flow gradient clamps against the flow size: the same here
-  const float gam_x = 1.f - t2.alpha, gam_y = 1.f - t2.beta;
-  const float* src = in1 + (size_t)b * C * plane;
-  const float* g = gout + (size_t)b * C * plane + (size_t)y * W + x;
-  long long* d1 = gxi + (size_t)b * C * plane;
-  float gdx = 0.f, gdy = 0.f;
-  for (int c = 0; c < C; ++c) {
-    const float gv = g[(size_t)c * plane];
-    long long* d = d1 + (size_t)c * plane;
-    fix_add(d + (size_t)t1.yT * W + t1.xL, (1.f - a1) * (1.f - b1) * gv, scale);
-    fix_add(d + (size_t)t1.yT * W + t1.xR, a1 * (1.f - b1) * gv, scale);
-    fix_add(d + (size_t)t1.yB * W + t1.xL, (1.f - a1) * b1 * gv, scale);
-    fix_add(d + (size_t)t1.yB * W + t1.xR, a1 * b1 * gv, scale);
-    const float* s = src + (size_t)c * plane;
-    const float iTL = s[(size_t)t2.yT * W + t2.xL], iTR = s[(size_t)t2.yT * W + t2.xR];
-    const float iBL = s[(size_t)t2.yB * W + t2.xL], iBR = s[(size_t)t2.yB * W + t2.xR];
-    gdx += gam_y * gv * iTR;
-    gdx -= gam_y * gv * iTL;
-    gdx += (1.f - gam_y) * gv * iBR;
-    gdx -= (1.f - gam_y) * gv * iBL;
-    gdy += gam_x * gv * iBL;
-    gdy -= gam_x * gv * iTL;
-    gdy += (1.f - gam_x) * gv * iBR;
-    gdy -= (1.f - gam_x) * gv * iTR;
-  }
-  gflow[((size_t)b * 2) * plane + (size_t)y * W + x] = gdx;
-  gflow[((size_t)b * 2 + 1) * plane + (size_t)y * W + x] = gdy;
+  if (idx >= (long long)B * H * W) return;
+  resample2d_bwd_pixel(in1, flow, gout, gflow, idx, C, H, W, H, W, [&](size_t i, float v) { fix_add(gxi + i, v, scale); });
 }
 
 size_t resample2d_bwd_det_workspace_bytes(int B, int C, int H, int W) {
@@ -678,19 +585,12 @@ extern "C" int pcfa_resample2d_bwd_det(const float* in1, const float* flow, cons
   if (workspace_bytes < resample2d_bwd_det_workspace_bytes(B, C, H, W)) return PCFA_ERR_WORKSPACE;
   if (reinterpret_cast<uintptr_t>(workspace) & 7) return PCFA_ERR_INVALID_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const long long nx = (long long)B * C * H * W, total = (long long)B * H * W;
-  long long* gxi = (long long*)workspace;
-  float* bmax = (float*)(gxi + nx);
-  const int nblk = (int)min((nx + 255) / 256, (long long)WARP_BMAX);
-  pcfa_launch(zero_ll_max_kernel, dim3(nblk), dim3(256), 0, s, gxi, grad_out, bmax, nx);
-  PCFA_LAUNCH_CHECK();
-  pcfa_launch(resample2d_bwd_det_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in1, flow, grad_out, gxi,
-              grad_flow, (const float*)bmax, nblk, B, C, H, W);
-  PCFA_LAUNCH_CHECK();
-  // grad_in1 = fixed point * unit, in index order (no flow partials: nf = 0)
-  pcfa_launch(pwc_warp_finish_kernel, dim3((int)min((nx + 255) / 256, 4096LL)), dim3(256), 0, s, (const long long*)gxi,
-              (const float*)nullptr, (const float*)bmax, nblk, grad_in1, (float*)nullptr, nx, 0LL, 1, 1.f, 1.f,
-              (long long)H * W);
-  PCFA_LAUNCH_CHECK();
-  return PCFA_OK;
+  const long long total = (long long)B * H * W;
+  auto scatter = [&](long long* gxi, float*, const float* bmax, int nblk) {
+    pcfa_launch(resample2d_bwd_det_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in1, flow, grad_out, gxi,
+                grad_flow, bmax, nblk, B, C, H, W);
+  };
+  // grad_in1 = fixed point * unit, in index order (no flow partials: nf = 0; the kernel wrote grad_flow itself)
+  return fixed_point_scatter(workspace, total * C, grad_out, scatter, grad_in1, (float*)nullptr, 0LL, 1, 1.f, 1.f,
+                             (long long)H * W, s);
 }

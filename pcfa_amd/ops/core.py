@@ -180,6 +180,13 @@ def _ptr_off(t, offset_floats):
     return ctypes.c_void_p(0 if t is None else t.data_ptr() + 4 * offset_floats)
 
 
+def scratch_for(size_fn, dims, device):
+    """(buffer, bytes) of the workspace that the library's `size_fn(*dims)` asks for: uninitialised int64 elements, so 8-byte
+    aligned, as the fixed-point scatters (PWC-Net / SpyNet warp, Resample2d backward) need it."""
+    nbytes = int(getattr(_hip.load(), size_fn)(*dims))
+    return torch.empty((nbytes + 7) // 8, device=device, dtype=torch.int64), nbytes
+
+
 def _pair(v):
     return (v, v) if isinstance(v, int) else tuple(v)
 

@@ -11,7 +11,7 @@ The weight transforms are plain tensor ops (tested on the host in float64):
 import torch
 
 from .. import _hip
-from .core import _call, _dev, _ptr, cached_pack
+from .core import _call, _dev, _ptr, cached_pack, scratch_for
 
 __all__ = ["GATHER_CK", "gather_tile", "gather_pack", "parity_offsets", "parity_weights", "conv_s2_leaky",
            "deconv4s2_leaky", "resample2d_det", "upsample_nearest4", "leaky_relu", "conv_s2_leaky_covers"]
@@ -214,8 +214,7 @@ class _Resample2dDet(torch.autograd.Function):
         B, C, H, W = ctx.dims
         g = g.contiguous()
         g1, g2 = torch.empty_like(input1), torch.empty_like(input2)
-        nws = int(_hip.load().pcfa_resample2d_bwd_det_workspace_bytes(B, C, H, W))
-        ws = torch.empty((nws + 7) // 8, device=g.device, dtype=torch.int64)
+        ws, nws = scratch_for("pcfa_resample2d_bwd_det_workspace_bytes", (B, C, H, W), g.device)
         _call("pcfa_resample2d_bwd_det", _ptr(input1), _ptr(input2), _ptr(g), _ptr(g1), _ptr(g2), _ptr(ws), nws, B, C, H, W)
         return g1, g2
 

@@ -121,8 +121,7 @@ class _PwcWarp(torch.autograd.Function):
         gx, gf = torch.empty_like(x), torch.empty_like(flo)
         if ctx.deterministic:   # fixed-point scatter (bit-reproducible); else hardware fp32 atomics
             B, C, H, W, thr, fs = ctx.params
-            nws = int(_hip.load().pcfa_pwc_warp_bwd_det_workspace_bytes(B, C, H, W))
-            ws = torch.empty((nws + 7) // 8, device=x.device, dtype=torch.int64)
+            ws, nws = core.scratch_for("pcfa_pwc_warp_bwd_det_workspace_bytes", (B, C, H, W), x.device)
             _call("pcfa_pwc_warp_bwd_det", _ptr(x), _ptr(flo), _ptr(g), _ptr(gx), _ptr(gf), _ptr(ws), nws, B, C, H, W,
                   thr, fs)
         else:

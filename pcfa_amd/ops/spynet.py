@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from .. import _hip
-from .core import _call, _dev, _ptr, cached_pack
+from .core import _call, _dev, _ptr, cached_pack, scratch_for
 from .flownet2 import gather_pack, gather_tile
 
 __all__ = ["conv7x7", "conv7x7_dgrad_weight", "conv7x7_pack", "conv7x7_tile", "spynet_warp", "spynet_warp_scales"]
@@ -122,8 +122,7 @@ class _SpyNetWarp(torch.autograd.Function):
         B, C, H, W, sx, sy = ctx.params
         g = g.contiguous()
         gx, gf = torch.empty_like(x), torch.empty_like(flo)
-        nws = int(_hip.load().pcfa_spynet_warp_bwd_workspace_bytes(B, C, H, W))
-        ws = torch.empty((nws + 7) // 8, device=x.device, dtype=torch.int64)
+        ws, nws = scratch_for("pcfa_spynet_warp_bwd_workspace_bytes", (B, C, H, W), x.device)
         _call("pcfa_spynet_warp_bwd", _ptr(x), _ptr(flo), _ptr(hor), _ptr(ver), _ptr(g), _ptr(gx), _ptr(gf), _ptr(ws), nws,
               *ctx.params)
         return gx, gf, None, None

@@ -772,6 +772,35 @@ def test_pwc_warp_vs_oracle(oracle_ops, shape, scale):
     assert max_abs(hip_ops.pwc_warp(xg.detach(), fg.detach(), flow_scale=0.625), ws) <= 2e-6 * float(x.detach().abs().max())
 
 
+@pytest.mark.parametrize("tearing", [False, True])
+@pytest.mark.parametrize("shape", [(1, 5, 7, 9), (1, 4, 40, 72), (2, 5, 33, 70)])
+def test_pwc_warp_atomic_and_fixed_point_backward_share_the_flow_gradient_bits(shape, tearing):
+    """the backward kernels form the flow gradient from one statement of the sample and of the per-channel
+    body (csrc/warp_ops.hip: warp_sample, warp_scatter), so with ONE channel group (C < 8: every channel in one thread, no
+    partial sums to add) the fp32-atomic and the fixed-point backward return the same BITS of grad_flo -- on the linear
+    thread map (plane < 256), the tile / window map, and ragged tiles at batch 2; a smooth flow, and a tearing one (taps leave
+    the window, the mask zeroes pixels).  grad_x differs by the rounding of the addends (rel-L2 < 1e-6, as
+    test_pwc_warp_vs_oracle asks)."""
+    B, C, H, W = shape
+    g = torch.Generator().manual_seed(H * W + C)
+    x = torch.randn(*shape, generator=g).to(DEV).requires_grad_(True)
+    go = torch.randn(*shape, generator=g).to(DEV)
+    if tearing:
+        f = 40.0 * torch.randn(B, 2, H, W, generator=g)
+    else:
+        f = torch.nn.functional.interpolate(3.0 * torch.randn(B, 2, max(H // 8, 1), max(W // 8, 1), generator=g), size=(H, W),
+                                            mode="bilinear", align_corners=False)
+    flo = f.contiguous().to(DEV).requires_grad_(True)
+    res = [torch.autograd.grad(hip_ops.pwc_warp(x, flo, deterministic=det, flow_scale=1.25), (x, flo), go)
+           for det in (True, False)]
+    if tearing:
+        assert bool((res[0][1] == 0).any())      # the mask zeroes pixels
+    else:
+        assert float(res[0][1].abs().max()) > 0
+    assert torch.equal(res[0][1].view(torch.int32), res[1][1].view(torch.int32))
+    assert rel_l2(res[1][0], res[0][0]) < 1e-6
+
+
 @pytest.mark.parametrize("bad", [float("nan"), float("inf"), -float("inf")])
 def test_pwc_warp_deterministic_backward_propagates_non_finite_gradients(bad):
     """the fixed-point scatter has no image of Inf / NaN (fmaxf drops NaN, the int64 conversion saturates), so
