@@ -20,6 +20,7 @@
 // optionally ReLU, stores 2x2 pixels.
 #include "common.hpp"
 #include "conv3x3_f43.hpp"
+#include "conv_tail.hpp"
 #include <cstdlib>
 
 namespace {
@@ -164,7 +165,6 @@ __global__ __launch_bounds__(256 * MT * KS) __attribute__((amdgpu_waves_per_eu(K
     addend = nullptr;
   }
   const int mask_n = second.mask_n;
-  const float mslope = ACT == 0 ? slope : 0.f;   // data gradients run without an activation: `slope` is the mask's
   const int n0 = nby * CBT;
   if (n0 >= N) return;  // (the packing pads N to 64: a 32-channel block may lie entirely in the padding)
   const long long plane = (long long)H * W;
@@ -418,42 +418,28 @@ __global__ __launch_bounds__(256 * MT * KS) __attribute__((amdgpu_waves_per_eu(K
         t1[j] = m[4 + j] - m[8 + j] - m[12 + j];
       }
       const float bv = (bias != nullptr && n < N) ? bias[n] : 0.f;
-      float y00 = t0[0] + t0[1] + t0[2] + bv, y01 = t0[1] - t0[2] - t0[3] + bv;
-      float y10 = t1[0] + t1[1] + t1[2] + bv, y11 = t1[1] - t1[2] - t1[3] + bv;
-      if (ACT == 1) {
-        y00 = fmaxf(y00, 0.f); y01 = fmaxf(y01, 0.f); y10 = fmaxf(y10, 0.f); y11 = fmaxf(y11, 0.f);
-      } else if (ACT == 2) {  // torch: x > 0 ? x : x * negative_slope
-        y00 = y00 > 0.f ? y00 : y00 * slope; y01 = y01 > 0.f ? y01 : y01 * slope;
-        y10 = y10 > 0.f ? y10 : y10 * slope; y11 = y11 > 0.f ? y11 : y11 * slope;
-      }
+      const float y00 = t0[0] + t0[1] + t0[2] + bv, y01 = t0[1] - t0[2] - t0[3] + bv;
+      const float y10 = t1[0] + t1[1] + t1[2] + bv, y11 = t1[1] - t1[2] - t1[3] + bv;
       if (n < N && oy < H && ox < W && worker) {
         const long long oo = (long long)n * plane + (long long)oy * W + ox;
-        // data gradient w.r.t. a (Leaky)ReLU output: the deferred activation backward of the producer, factor 1 where its
-        // output is positive, else the producer's slope (0: ReLU, written as an exact zero)
-        auto masked = [&](float v, float m) { return m > 0.f ? v : (mslope == 0.f ? 0.f : v * mslope); };
-        if (mask != nullptr && mask_n == 0) {
-          y00 = masked(y00, mk[q][0]); y01 = masked(y01, mk[q][1]); y10 = masked(y10, mk[q][2]); y11 = masked(y11, mk[q][3]);
-        }
-        if (addend != nullptr) {   // the other consumer's gradient of the same tensor, summed here instead of by autograd
-          y00 += ad[q][0]; y01 += ad[q][1]; y10 += ad[q][2]; y11 += ad[q][3];
-        }
-        if (mask != nullptr && mask_n > 0 && n < mask_n) {   // the gradient is complete only with the addend
-          y00 = masked(y00, mk[q][0]); y01 = masked(y01, mk[q][1]); y10 = masked(y10, mk[q][2]); y11 = masked(y11, mk[q][3]);
-        }
+        // (the addend: the other consumer's gradient of the same tensor, summed here instead of by autograd)
+        const bool mall = mask != nullptr && mask_n == 0, mpre = mask != nullptr && mask_n > 0 && n < mask_n;
+        const bool add = addend != nullptr;
+        const float4 y = conv_tail<ACT>(make_float4(y00, y01, y10, y11), slope, mall, mpre,
+                                        [&] { return make_float4(mk[q][0], mk[q][1], mk[q][2], mk[q][3]); }, add,
+                                        [&] { return make_float4(ad[q][0], ad[q][1], ad[q][2], ad[q][3]); });
         float* o = out + oo;
-        o[0] = y00;
-        if (ox + 1 < W) o[1] = y01;
+        o[0] = y.x;
+        if (ox + 1 < W) o[1] = y.y;
         if (oy + 1 < H) {
-          o[W] = y10;
-          if (ox + 1 < W) o[W + 1] = y11;
+          o[W] = y.z;
+          if (ox + 1 < W) o[W + 1] = y.w;
         }
       }
     }
     __syncthreads();
   }
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -486,7 +472,8 @@ extern "C" int pcfa_conv3x3_pack_weights(const float* w, float* fwd_packed, floa
   return PCFA_OK;
 }
 
-// dx = dy * (out > 0 ? 1 : slope): backward of LeakyReLU from its OUTPUT (same sign as the input for slope > 0)
+// dx = dy * (out > 0 ? 1 : slope): backward of LeakyReLU from its OUTPUT (same sign as the input for slope > 0).  A PRODUCT
+// at slope 0 too, unlike conv_tail.hpp's deferred_mask, which selects an exact zero there.
 __global__ void leaky_relu_bwd_kernel(const float* __restrict__ out, const float* __restrict__ g, float* __restrict__ gx,
                                       float slope, long long n) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
@@ -495,7 +482,7 @@ __global__ void leaky_relu_bwd_kernel(const float* __restrict__ out, const float
 
 __global__ void leaky_relu_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, float slope, long long n) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-    y[i] = x[i] > 0.f ? x[i] : x[i] * slope;
+    y[i] = act_apply<2>(x[i], slope);
 }
 
 #ifdef PCFA_C3_STAMPS

@@ -26,6 +26,7 @@
 // 24 MFMAs per wave and chunk, one barrier per chunk.  Group 1's sums meet group 0's in the epilogue's LDS image.
 #include "common.hpp"
 #include "conv3x3_f43.hpp"
+#include "conv_tail.hpp"
 #include <cstdlib>
 
 namespace {
@@ -365,26 +366,9 @@ __global__ __launch_bounds__(NTG * NGT) void conv3x3_f43_kernel(
             const long long oo = (long long)n * plane + (long long)(oy + p) * W + ox;
             float4 y = make_float4(yv[p][0] + bv, yv[p][1] + bv, yv[p][2] + bv, yv[p][3] + bv);
             if (!PARTIAL) {
-              if (ACT == 1) {
-                y.x = fmaxf(y.x, 0.f); y.y = fmaxf(y.y, 0.f); y.z = fmaxf(y.z, 0.f); y.w = fmaxf(y.w, 0.f);
-              } else if (ACT == 2) {
-                y.x = y.x > 0.f ? y.x : y.x * slope; y.y = y.y > 0.f ? y.y : y.y * slope;
-                y.z = y.z > 0.f ? y.z : y.z * slope; y.w = y.w > 0.f ? y.w : y.w * slope;
-              }
-              const float ms = ACT == 0 ? slope : 0.f;   // mask factor where the producer's output is not positive
-              auto masked = [&](float v, float m) { return m > 0.f ? v : (ms == 0.f ? 0.f : v * ms); };
-              if (mask != nullptr && mask_n == 0) {
-                const float4 mk = *reinterpret_cast<const float4*>(mask + oo);
-                y.x = masked(y.x, mk.x); y.y = masked(y.y, mk.y); y.z = masked(y.z, mk.z); y.w = masked(y.w, mk.w);
-              }
-              if (addend != nullptr) {
-                const float4 ad = *reinterpret_cast<const float4*>(addend + oo);
-                y.x += ad.x; y.y += ad.y; y.z += ad.z; y.w += ad.w;
-              }
-              if (mask != nullptr && mask_n > 0 && n < mask_n) {   // channel prefix, after the addend (conv3x3.hip)
-                const float4 mk = *reinterpret_cast<const float4*>(mask + oo);
-                y.x = masked(y.x, mk.x); y.y = masked(y.y, mk.y); y.z = masked(y.z, mk.z); y.w = masked(y.w, mk.w);
-              }
+              const bool mall = mask != nullptr && mask_n == 0, mpre = mask != nullptr && mask_n > 0 && n < mask_n;
+              y = conv_tail<ACT>(y, slope, mall, mpre, [&] { return *reinterpret_cast<const float4*>(mask + oo); },
+                                 addend != nullptr, [&] { return *reinterpret_cast<const float4*>(addend + oo); });
             }
             *reinterpret_cast<float4*>(ob + oo) = y;
           }
@@ -415,31 +399,12 @@ __global__ __launch_bounds__(256) void f43_finish_kernel(const float* __restrict
       const float bv = bias[(int)((i / plane4) % N)];
       y.x += bv; y.y += bv; y.z += bv; y.w += bv;
     }
-    if (ACT == 1) {
-      y.x = fmaxf(y.x, 0.f); y.y = fmaxf(y.y, 0.f); y.z = fmaxf(y.z, 0.f); y.w = fmaxf(y.w, 0.f);
-    } else if (ACT == 2) {
-      y.x = y.x > 0.f ? y.x : y.x * slope; y.y = y.y > 0.f ? y.y : y.y * slope;
-      y.z = y.z > 0.f ? y.z : y.z * slope; y.w = y.w > 0.f ? y.w : y.w * slope;
-    }
-    const float ms = ACT == 0 ? slope : 0.f;
-    auto masked = [&](float v, float m) { return m > 0.f ? v : (ms == 0.f ? 0.f : v * ms); };
-    if (mask != nullptr && mask_n == 0) {
-      const float4 mk = reinterpret_cast<const float4*>(mask)[i];
-      y.x = masked(y.x, mk.x); y.y = masked(y.y, mk.y); y.z = masked(y.z, mk.z); y.w = masked(y.w, mk.w);
-    }
-    if (addend != nullptr) {
-      const float4 ad = reinterpret_cast<const float4*>(addend)[i];
-      y.x += ad.x; y.y += ad.y; y.z += ad.z; y.w += ad.w;
-    }
-    if (mask != nullptr && mask_n > 0 && (int)((i / plane4) % N) < mask_n) {
-      const float4 mk = reinterpret_cast<const float4*>(mask)[i];
-      y.x = masked(y.x, mk.x); y.y = masked(y.y, mk.y); y.z = masked(y.z, mk.z); y.w = masked(y.w, mk.w);
-    }
+    const bool mall = mask != nullptr && mask_n == 0, mpre = mask != nullptr && mask_n > 0 && (int)((i / plane4) % N) < mask_n;
+    y = conv_tail<ACT>(y, slope, mall, mpre, [&] { return reinterpret_cast<const float4*>(mask)[i]; }, addend != nullptr,
+                       [&] { return reinterpret_cast<const float4*>(addend)[i]; });
     reinterpret_cast<float4*>(out)[i] = y;
   }
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 

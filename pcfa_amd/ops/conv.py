@@ -119,6 +119,19 @@ def conv_s2_supported(x, weight):
                 and _hip.load().pcfa_conv_s2_supported(Cin, N, kh, x.shape[2], x.shape[3]))
 
 
+def _act_bwd(out, g, act, slope=0.):
+    """The gradient w.r.t. the pre-activation of out = act(.) from the gradient g w.r.t. out (act: 0 none -- g itself --,
+    1 ReLU, 2 LeakyReLU(slope)): the un-fused form of csrc/conv_tail.hpp's mask, one streaming launch."""
+    if not act:
+        return g
+    gm = torch.empty_like(g)
+    if act == 1:
+        _call("pcfa_relu_bwd", _ptr(out), _ptr(g), _ptr(gm), g.numel())
+    else:
+        _call("pcfa_leaky_relu_bwd", _ptr(out), _ptr(g), _ptr(gm), float(slope), g.numel())
+    return gm
+
+
 class _ConvS2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, act, slope, grad_premasked=False, own_bwd=True):
@@ -140,13 +153,8 @@ class _ConvS2(torch.autograd.Function):
     def backward(ctx, g):
         weight, out = ctx.saved_tensors
         g = g.contiguous()
-        if ctx.act and not ctx.grad_premasked:
-            gm = torch.empty_like(g)
-            if ctx.act == 1:
-                _call("pcfa_relu_bwd", _ptr(out), _ptr(g), _ptr(gm), g.numel())
-            else:
-                _call("pcfa_leaky_relu_bwd", _ptr(out), _ptr(g), _ptr(gm), ctx.slope, g.numel())
-            g = gm
+        if not ctx.grad_premasked:
+            g = _act_bwd(out, g, ctx.act, ctx.slope)
         N, Cin, k, _ = weight.shape
         B, _, H, W = ctx.xshape
         if ctx.own_bwd and _hip.load().pcfa_conv_s2_bwd_supported(Cin, N, k, H, W):
@@ -206,10 +214,7 @@ class _ConvS2DS(torch.autograd.Function):
         B, Cin, H, W = ctx.xshape
         g = g.contiguous()
         gd = gd.contiguous()
-        if ctx.act:
-            gm = torch.empty_like(g)
-            _call("pcfa_relu_bwd", _ptr(out), _ptr(g), _ptr(gm), g.numel())
-            g = gm
+        g = _act_bwd(out, g, ctx.act)
         gx = torch.empty(ctx.xshape, device=g.device, dtype=torch.float32)
         _call("pcfa_conv_s2_ds_bwd", _ptr(g), _ptr(gd), _ptr(ctx.packed_bwd), _ptr(gx), B, Cin, g.shape[1], H, W)
         return gx, None, None, None, None, None
@@ -512,13 +517,7 @@ class _Conv3x3(torch.autograd.Function):
             return (None if g_skip is None else g_skip), None, None, None, None, None, None, None
         g = g.contiguous()
         if ctx.act and not ctx.grad_premasked:
-            out = ctx.saved_tensors[0]
-            gm = torch.empty_like(g)
-            if ctx.act == 1:
-                _call("pcfa_relu_bwd", _ptr(out), _ptr(g), _ptr(gm), g.numel())
-            else:
-                _call("pcfa_leaky_relu_bwd", _ptr(out), _ptr(g), _ptr(gm), ctx.slope, g.numel())
-            g = gm
+            g = _act_bwd(ctx.saved_tensors[0], g, ctx.act, ctx.slope)
         gin = torch.empty((B, K, H, W), device=g.device, dtype=torch.float32)
         if g_skip is not None or ctx.mask_input_grad:
             xin = ctx.saved_tensors[-1] if ctx.mask_input_grad else None   # = a (Leaky)ReLU output: [xin > 0] is its mask

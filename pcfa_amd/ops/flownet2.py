@@ -125,9 +125,8 @@ class _ConvS2Leaky(torch.autograd.Function):
         gx = torch.empty(ctx.xshape, device=g.device, dtype=torch.float32)
         lib = _hip.load()
         if lib.pcfa_conv_s2_bwd_supported(cin, cout, k, H, W):
-            from .conv import _s2_bwd_packed
-            gm = torch.empty_like(g)
-            _call("pcfa_leaky_relu_bwd", _ptr(out), _ptr(g), _ptr(gm), ctx.slope, g.numel())
+            from .conv import _act_bwd, _s2_bwd_packed
+            gm = _act_bwd(out, g, 2, ctx.slope)
             _call("pcfa_conv_s2_bwd", _ptr(gm), _ptr(_s2_bwd_packed(weight)), _ptr(gx), B, cin, cout, H, W, k)
         else:
             t = (k + 1) // 2

@@ -295,6 +295,48 @@ def test_conv3x3_run_epilogues(record_property, shape, variant):
     run_conv3x3(record_property, *shape, bias=False, backward=True, **kw)
 
 
+TAIL_PATHS = {(1, 64, 64, 55, 64): "f23_ks2", (1, 21, 37, 30, 68): "f23_plain_partial", (1, 96, 64, 24, 80): "f23_ksliced",
+              (1, 192, 64, 48, 64): "f43_split", (1, 80, 192, 64, 256): "f43_direct"}
+
+
+@pytest.mark.parametrize("shape", list(TAIL_PATHS), ids=_sid)
+def test_conv3x3_tail_nonfinite_under_zero_mask(shape):
+    """The tail's select at slope 0 (csrc/conv_tail.hpp), as a data gradient on every place that finishes an output: the
+    gradient holds one +inf and one NaN, the mask is non-positive everywhere (negatives, +0.0, -0.0).
+    a. mask on every channel, then the addend: the output IS the addend, bit for bit -- the convolution's value, finite or
+       not, became an exact zero.  b. mask on a channel prefix after the addend: +0.0 bits in every masked channel.
+    c. the same with slope 0.1: a non-zero factor multiplies, so the +inf element's pixel is non-finite in every channel."""
+    B, K, N, H, W = shape
+    assert wg.conv3x3_path(*shape, env={}) == TAIL_PATHS[shape]
+    lib = _lib()
+    gen = torch.Generator().manual_seed(K * 131 + N)
+    g = torch.randn(B, K, H, W, generator=gen)
+    y, x = H // 2, W // 2
+    g[0, 1, y, x], g[0, K - 2, H // 3, W // 3] = float("inf"), float("nan")
+    wt = torch.randn(K, N, 3, 3, generator=gen) / (9 * K) ** .5
+    ad = torch.randn(B, N, H, W, generator=gen)
+    sel = torch.randint(0, 3, (B, N, H, W), generator=gen)
+    mk = torch.where(sel == 1, torch.zeros(()), -1 - torch.rand(B, N, H, W, generator=gen))
+    mk = torch.where(sel == 2, torch.full((), -0.0), mk)
+    _, fp = pack_conv3x3(wt, K, N, True)
+    fg, fm, fa = (Fenced(t.shape, _dense_stride(t.shape), NAN_BITS).write(t) for t in (g, mk, ad))
+    wbytes = int(lib.pcfa_conv3x3_workspace_bytes(*shape))
+    fws = Fenced((wbytes // 4,), (1,), NAN_BITS) if wbytes else None
+
+    def run(slope, mask_channels):
+        fo = Fenced((B, N, H, W), _dense_stride((B, N, H, W)), SENTINEL)
+        assert lib.pcfa_conv3x3_run(fg.ptr(), fp.ptr(), None, fm.ptr(), fa.ptr(), fo.ptr(), B, K, N, H, W, 0, slope,
+                                    mask_channels, fws.ptr() if fws else None, wbytes, stream()) == 0
+        torch.cuda.synchronize()
+        assert fo.fence_intact() and (fws is None or fws.fence_intact()), "a store landed outside its buffer"
+        return fo.view().cpu()
+
+    m = N // 2 + 3
+    assert torch.equal(run(0.0, 0).view(torch.int32), ad.view(torch.int32)), "a: output != addend"
+    assert not bool(run(0.0, m)[:, :m].view(torch.int32).any()), "b: a masked channel holds other bits than +0.0"
+    assert not bool(torch.isfinite(run(SLOPE, m)[0, :, y, x]).any()), "c: slope 0.1 selected instead of multiplying"
+
+
 @pytest.mark.parametrize("entry", ["fwd", "act_fwd", "masked_fwd", "fused_bwd"])
 @pytest.mark.parametrize("shape", [(1, 64, 64, 55, 64), (1, 21, 37, 30, 68), (2, 2, 3, 2, 3)], ids=_sid)
 def test_conv3x3_older_entries(record_property, shape, entry):
