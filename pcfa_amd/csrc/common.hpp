@@ -120,6 +120,30 @@ __device__ __forceinline__ float block_max_256(float m, float* red) {
   __syncthreads();
   return m;
 }
+
+// Zero fill of N float buffers in one launch, grid-stride, four floats per thread and step (one 16-byte store where the
+// buffer is aligned and four floats remain).  Any 1-D grid of any block size.  A kernel, not hipMemsetAsync: inside torch's
+// stream capture the memset node was not replayed with the graph (stale gradients accumulated from replay to replay).
+template <int N>
+struct ZeroSpans {
+  float* p[N];
+  long long n[N];
+};
+template <int N>
+__global__ void zero_fill_kernel(ZeroSpans<N> z) {
+  const long long step = (long long)gridDim.x * blockDim.x * 4;
+  for (int b = 0; b < N; ++b) {
+    float* p = z.p[b];
+    const long long n = z.n[b];
+    for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += step) {
+      if (i + 3 < n && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+        *reinterpret_cast<float4*>(p + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+      } else {
+        for (long long k = i; k < n && k < i + 4; ++k) p[k] = 0.f;
+      }
+    }
+  }
+}
 #endif
 
 // ---- measurement hook -----------------------------------------------------------------------------------

@@ -28,20 +28,19 @@
 //              window position lane d (channels d, d+64, ..): dfmap1 += dC * f2_l(p) in registers (the query owns it: a
 //              plain read-modify-write, no atomics), and df2_l(p) += dC * f1(q) as fixed-point int64 atomics, one 512-B
 //              contiguous wave-instruction per 64 channels.  A convert pass then adds acc into df2 in fp32 and re-zeroes acc.
-// Fixed point (deterministic: integer adds commute): the unit of a lookup's backward is 2^-shift with
+// Fixed point (fixed_point.hpp): the unit of a lookup's backward is 2^-shift with
 //   shift = 61 - ceil(log2 Q) - (ilogb(M) + 1),  M = 2 * max|grad_out| * max|fmap1| / sqrt(D),
 // since |dC| <= max|grad_out| / sqrt(D) (the bilinear weights a position receives sum to <= 1) and at most Q queries of one
 // image add into one position: |sum| < 2^61.  Every addend keeps >= 61 - log2(Q) bits below the largest (>= 41 at 8K).
-// A non-finite max|grad_out| or max|fmap1| flags the lookup: no scatter, and the convert pass writes NaN into all of df2
-// (dfmap2 is then NaN everywhere, never a finite wrong value; dfmap1 carries the NaN through its fp32 sums).
+// Either maximum can flag the lookup; dfmap1 then carries the NaN through its fp32 sums.
 #include "common.hpp"
+#include "fixed_point.hpp"
 
 namespace {
 
 constexpr int OD_NBLK = 256;            // block maxima per |x| reduction
 constexpr int OD_QT = 16;               // queries per forward workgroup
 constexpr int OD_KMAX = 8;              // channels per lane in the backward: D <= 512
-constexpr int OD_NONFINITE = -(1 << 20);
 
 struct OdLayout {
   int B, D, H, W, L, Q;
@@ -143,38 +142,21 @@ __global__ __launch_bounds__(256) void od_pool_kernel(const float* __restrict__ 
   }
 }
 
-__global__ __launch_bounds__(256) void od_zero_kernel(float* __restrict__ p, long long n) {
-  const long long step = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) p[i] = 0.f;
-}
-
-// bmax[block] = max |x| over the block's grid-stride share; +inf for a block that saw Inf / NaN (the flag)
 __global__ __launch_bounds__(256) void od_absmax_kernel(const float* __restrict__ x, long long n, float* __restrict__ bmax) {
   __shared__ float red[4];
-  const long long step = (long long)gridDim.x * blockDim.x;
-  float m = 0.f;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
-    const float v = fabsf(x[i]);
-    m = (v <= 3.0e38f) ? fmaxf(m, v) : __int_as_float(0x7f800000);
-  }
-  m = block_max_256(m, red);
-  if (threadIdx.x == 0) bmax[blockIdx.x] = m;
+  fix_absmax_share(x, n, bmax, red, [](long long) {});
 }
 
 // the fixed-point exponent of one lookup's backward (header comment); one block of 256 threads
 __global__ __launch_bounds__(256) void od_shift_kernel(const float* __restrict__ f1max, const float* __restrict__ gmax,
                                                        int log2q, float inv_sqrt_d, int* __restrict__ shift) {
   __shared__ float red[4];
-  float a = 0.f, g = 0.f;
-  for (int i = threadIdx.x; i < OD_NBLK; i += 256) {
-    a = fmaxf(a, f1max[i]);
-    g = fmaxf(g, gmax[i]);
-  }
-  a = block_max_256(a, red);
-  g = block_max_256(g, red);
+  float a = fix_bmax_share(f1max, OD_NBLK), g = fix_bmax_share(gmax, OD_NBLK);
+  a = fix_block_absmax(a, red);
+  g = fix_block_absmax(g, red);
   if (threadIdx.x != 0) return;
-  if (!(a < 3.0e38f) || !(g < 3.0e38f)) {
-    *shift = OD_NONFINITE;
+  if (a == fix_inf() || g == fix_inf()) {
+    *shift = FIX_NONFINITE;
     return;
   }
   const double M = 2.0 * (double)a * (double)g * (double)inv_sqrt_d;
@@ -276,8 +258,8 @@ __global__ __launch_bounds__(256) void od_bwd_kernel(OdLayout Lo, const float* _
   const bool live = q < Q;
   const int qc = live ? q : Q - 1;
   const int shift = *shiftp;
-  const bool scatter = live && shift != OD_NONFINITE;
-  const double scale = ldexp(1.0, shift == OD_NONFINITE ? 0 : shift);
+  const bool scatter = live && shift != FIX_NONFINITE;
+  const double scale = ldexp(1.0, shift == FIX_NONFINITE ? 0 : shift);
   const float* f1 = f1t + ((size_t)b * Q + qc) * D;
   float f1v[OD_KMAX], g1[OD_KMAX];
 #pragma unroll
@@ -334,9 +316,7 @@ __global__ __launch_bounds__(256) void od_bwd_kernel(OdLayout Lo, const float* _
         const int d = lane + 64 * k;
         if (d < D) {
           gl[k] = fmaf(dc, lvl[ro + d], gl[k]);
-          if (scatter)
-            atomicAdd(reinterpret_cast<unsigned long long*>(alvl + ro + d),
-                      (unsigned long long)__double2ll_rn(dcs * (double)f1v[k]));
+          if (scatter) fix_add(alvl + ro + d, f1v[k], dcs);   // f1 * (dC * 2^shift): the position's scale
         }
       }
     }
@@ -357,11 +337,11 @@ __global__ __launch_bounds__(256) void od_bwd_kernel(OdLayout Lo, const float* _
 __global__ __launch_bounds__(256) void od_convert_kernel(long long* __restrict__ acc, float* __restrict__ df2, long long n,
                                                          const int* __restrict__ shiftp, int accumulate) {
   const int shift = *shiftp;
-  const bool bad = shift == OD_NONFINITE;
+  const bool bad = shift == FIX_NONFINITE;
   const double inv = ldexp(1.0, bad ? 0 : -shift);
   const long long step = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
-    const float v = bad ? __int_as_float(0x7fc00000) : (float)((double)acc[i] * inv);
+    const float v = bad ? fix_qnan() : fix_to_float(acc[i], inv);
     df2[i] = accumulate ? df2[i] + v : v;
     acc[i] = 0;
   }
@@ -458,11 +438,12 @@ extern "C" int pcfa_corr_ondemand_prepare(const float* fmap1, const float* fmap2
                 pyr + Lo.prow[l] * D, Lo.h[l - 1], Lo.w[l - 1], Lo.h[l], Lo.w[l], D, n);
     PCFA_LAUNCH_CHECK();
   }
-  pcfa_launch(od_zero_kernel, dim3(1), dim3(256), 0, s, pyr + Lo.rows * D, (long long)D);
+  pcfa_launch(zero_fill_kernel<1>, dim3(1), dim3(256), 0, s, ZeroSpans<1>{{pyr + Lo.rows * D}, {(long long)D}});
   PCFA_LAUNCH_CHECK();
   // the fixed-point accumulator starts at 0; each bwd's convert pass leaves it at 0 again
   const long long nacc = 2 * Lo.rows * D;
-  pcfa_launch(od_zero_kernel, dim3(stride_grid(nacc)), dim3(256), 0, s, at<float>(workspace, Lo.o_acc), nacc);
+  pcfa_launch(zero_fill_kernel<1>, dim3(stride_grid(nacc)), dim3(256), 0, s,
+              ZeroSpans<1>{{at<float>(workspace, Lo.o_acc)}, {nacc}});
   PCFA_LAUNCH_CHECK();
   pcfa_launch(od_absmax_kernel, dim3(OD_NBLK), dim3(256), 0, s, fmap1, (long long)B * D * Lo.Q,
               at<float>(workspace, Lo.o_f1max));

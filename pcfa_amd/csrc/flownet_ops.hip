@@ -452,19 +452,6 @@ __global__ void channelnorm_bwd_kernel(const float* __restrict__ in, const float
   gin[idx] = (float)((double)(gout[b * plane + p] * in[idx]) / ((double)out[b * plane + p] + 1e-9));
 }
 
-// grad_in1 of Resample2d is cleared by a kernel, not hipMemsetAsync: inside torch's stream capture the memset node
-// was not replayed with the graph (stale gradients accumulated from replay to replay), a kernel node is.
-__global__ void zero_fill_kernel(float* __restrict__ p, long long n) {
-  const long long step = (long long)gridDim.x * blockDim.x * 4;
-  for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += step) {
-    if (i + 3 < n && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
-      *reinterpret_cast<float4*>(p + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-    } else {
-      for (long long k = i; k < n && k < i + 4; ++k) p[k] = 0.f;
-    }
-  }
-}
-
 int blocks_for(long long total, int threads) {
   const long long n = (total + threads - 1) / threads;
   return (int)(n < 65535LL * 32 ? n : 65535LL * 32);
@@ -562,7 +549,7 @@ extern "C" int pcfa_resample2d_bwd(const float* in1, const float* flow, const fl
   if (kernel_size != 1 || H > iH || W > iW) return PCFA_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   const long long n1 = (long long)B * C * iH * iW;
-  pcfa_launch(zero_fill_kernel, dim3(blocks_for((n1 + 3) / 4, 256)), dim3(256), 0, s, grad_in1, n1);
+  pcfa_launch(zero_fill_kernel<1>, dim3(blocks_for((n1 + 3) / 4, 256)), dim3(256), 0, s, ZeroSpans<1>{{grad_in1}, {n1}});
   PCFA_LAUNCH_CHECK();
   const long long total = (long long)B * H * W;
   pcfa_launch(resample2d_bwd_kernel, dim3(blocks_for(total, 256)), dim3(256), 0, s, in1, flow, grad_out,

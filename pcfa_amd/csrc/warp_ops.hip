@@ -16,6 +16,7 @@
 // original PWC-Net code), the sample position is x * W / (W - 1) - 0.5.
 #include <cstdlib>
 #include "common.hpp"
+#include "fixed_point.hpp"
 #include "resample2d_taps.hpp"
 
 namespace {
@@ -190,7 +191,7 @@ __global__ __launch_bounds__(256) void pwc_warp_fwd_kernel(const float* __restri
   }
 }
 
-// grad_x must be zero on entry (cleared by zero2_kernel below); grad_flo likewise when G > 1.
+// grad_x must be zero on entry (cleared by zero_fill_kernel<2>); grad_flo likewise when G > 1.
 __global__ __launch_bounds__(256) void pwc_warp_bwd_kernel(const float* __restrict__ x, const float* __restrict__ flo,
                                                           const float* __restrict__ gout, float* __restrict__ gx,
                                                           float* __restrict__ gflo, int C, int H, int W,
@@ -223,33 +224,24 @@ __global__ __launch_bounds__(256) void pwc_warp_bwd_kernel(const float* __restri
   }
 }
 
-// Deterministic variant of the scatter: contributions are added as fixed-point int64 (integer adds commute and
-// associate, so the order in which the atomics land cannot change the sum: two runs give the same bits), the flow
-// gradient's channel groups write their partials side by side.  wfinish converts / adds in index order.
-// The fixed point is scaled PER CALL: with m = max|grad_out| (found by the kernel that clears the accumulators: block
-// maxima, re-reduced by every consumer block -- a maximum does not depend on the order either) the unit is
-// 2^(floor(log2 m) - 40), i.e. every addend keeps 40 bits below the largest gradient of the call (fp32 keeps 24 below
-// each value: values down to 1.5e-5 of the maximum are resolved as finely as fp32 resolves them, whatever the
-// absolute scale -- AEE / npix-scaled gradients of 1e-9 included), and 2^22 addends of maximal size fit an int64.
+// Deterministic variant of the scatter: contributions are added as fixed-point int64 (fixed_point.hpp: any order of the
+// atomics gives the same bits), the flow gradient's channel groups write their partials side by side.  wfinish converts /
+// adds in index order.
+// The fixed point is scaled PER CALL: with m = max|grad_out| (found by the kernel that clears the accumulators, re-reduced
+// by every consumer block) the unit is 2^(floor(log2 m) - 40), i.e. every addend keeps 40 bits below the largest gradient of
+// the call (fp32 keeps 24 below each value: values down to 1.5e-5 of the maximum are resolved as finely as fp32 resolves
+// them, whatever the absolute scale -- AEE / npix-scaled gradients of 1e-9 included), and 2^22 addends of maximal size fit
+// an int64.  A flagged call (non-finite grad_out) scatters with scale 0 and the finish kernel writes NaN into ALL of grad_x
+// and grad_flo: the optimiser sees the fault as it would after grid_sample's backward, which poisons only the taps of the
+// non-finite pixels.
 constexpr int WARP_FIX_BITS = 40;
 constexpr int WARP_BMAX = 4096;   // block maxima of |grad_out| (one per block of the clearing kernel)
-// A non-finite grad_out has no fixed-point image (fmaxf drops NaN, __double2ll_rn saturates): the call is flagged instead
-// -- the scatter kernels run with scale 0 (their sums are not used) and the finish kernel writes NaN into ALL of grad_x and
-// grad_flo, so that the optimiser sees the fault as it would after grid_sample's backward (which poisons only the taps of
-// the non-finite pixels: a superset here, never finite garbage).
-constexpr int WARP_NONFINITE = -(1 << 20);
 
 // 2^shift = the fixed-point scale of this call (uniform over the grid: every block reduces the same block maxima)
 __device__ __forceinline__ int warp_fix_shift(const float* __restrict__ bmax, int nblk, float* red) {
-  float m = 0.f;
-  for (int i = threadIdx.x; i < nblk; i += 256) m = fmaxf(m, bmax[i]);
-  m = block_max_256(m, red);
-  if (!(m < 3.0e38f)) return WARP_NONFINITE;   // zero_ll_max_kernel stores +inf for a block that saw Inf / NaN (or > 3e38)
+  const float m = fix_block_absmax(fix_bmax_share(bmax, nblk), red);
+  if (m == fix_inf()) return FIX_NONFINITE;
   return m > 0.f ? WARP_FIX_BITS - ilogbf(m) : WARP_FIX_BITS;
-}
-
-__device__ __forceinline__ void fix_add(long long* p, float v, double scale) {
-  atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double2ll_rn((double)v * scale));
 }
 
 // a channel group's share of d loss / d (scaled flow) before the finish multiplies by the scale:
@@ -346,7 +338,7 @@ __global__ __launch_bounds__(256) void pwc_warp_bwd_det_lds_kernel(
       if (c < C && act) {
         long long* gc = gb + (size_t)c * plane;
         warp_scatter(s, xb + (size_t)c * plane, go[(size_t)c * plane], gix, giy, [&](int tap, int o, float v) {
-          const unsigned long long q = (unsigned long long)__double2ll_rn((double)v * scale);
+          const unsigned long long q = fix_quantize(v, scale);
           if (cell[tap] >= 0) atomicAdd(&win[j][cell[tap]], q);
           else atomicAdd(reinterpret_cast<unsigned long long*>(gc + o), q);
         });
@@ -380,16 +372,15 @@ __global__ __launch_bounds__(256) void pwc_warp_finish_kernel(const long long* _
   __shared__ float red[4];
   const int shift = warp_fix_shift(bmax, nblk, red);
   const long long step = (long long)gridDim.x * blockDim.x;
-  if (shift == WARP_NONFINITE) {
-    const float qnan = __int_as_float(0x7fc00000);
+  if (shift == FIX_NONFINITE) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nx + nf; i += step)
-      (i < nx ? gx[i] : gflo[i - nx]) = qnan;
+      (i < nx ? gx[i] : gflo[i - nx]) = fix_qnan();
     return;
   }
   const double inv = ldexp(1.0, -shift);
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nx + nf; i += step) {
     if (i < nx) {
-      gx[i] = (float)((double)gxi[i] * inv);
+      gx[i] = fix_to_float(gxi[i], inv);
     } else {
       const long long j = i - nx;
       float s = gfpart[j];
@@ -404,23 +395,7 @@ __global__ __launch_bounds__(256) void pwc_warp_finish_kernel(const long long* _
 __global__ __launch_bounds__(256) void zero_ll_max_kernel(long long* __restrict__ a, const float* __restrict__ g,
                                                           float* __restrict__ bmax, long long n) {
   __shared__ float red[4];
-  const long long step = (long long)gridDim.x * blockDim.x;
-  float m = 0.f;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) {
-    a[i] = 0;
-    const float v = fabsf(g[i]);
-    m = (v <= 3.0e38f) ? fmaxf(m, v) : __int_as_float(0x7f800000);   // NaN fails the comparison too: +inf = the flag
-  }
-  m = block_max_256(m, red);
-  if (threadIdx.x == 0) bmax[blockIdx.x] = m;
-}
-
-__global__ void zero2_kernel(float* __restrict__ a, long long na, float* __restrict__ b, long long nb) {
-  const long long step = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < na + nb; i += step) {
-    if (i < na) a[i] = 0.f;
-    else b[i - na] = 0.f;
-  }
+  fix_absmax_share(g, n, bmax, red, [&](long long i) { a[i] = 0; });
 }
 
 int channel_groups(long long plane, int C) {
@@ -564,7 +539,7 @@ extern "C" int pcfa_pwc_warp_bwd(const float* x, const float* flo, const float* 
   const long long na = (long long)B * C * plane, nb = (long long)B * 2 * plane;
   long long zb = (na + nb + 255) / 256;
   if (zb > 4096) zb = 4096;
-  pcfa_launch(zero2_kernel, dim3((int)zb), dim3(256), 0, s, grad_x, na, grad_flo, nb);
+  pcfa_launch(zero_fill_kernel<2>, dim3((int)zb), dim3(256), 0, s, ZeroSpans<2>{{grad_x, grad_flo}, {na, nb}});
   PCFA_LAUNCH_CHECK();
   dim3 grid(pcfa_cdiv(plane, 256), channel_groups(plane, C), B);
   pcfa_launch(pwc_warp_bwd_kernel, grid, dim3(256), 0, s, x, flo, grad_out, grad_x, grad_flo, C, H, W,

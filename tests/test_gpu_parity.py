@@ -821,6 +821,51 @@ def test_pwc_warp_deterministic_backward_propagates_non_finite_gradients(bad):
     assert torch.equal(again[0], good[0]) and torch.equal(again[1], good[1])
 
 
+@pytest.mark.parametrize("special", [float("inf"), float("-inf"), float("nan"), 3.0e38, 3.3e38])
+def test_fixed_point_flag_is_one_rule_for_warp_resample_and_ondemand(special):
+    """csrc/fixed_point.hpp: the three fixed-point backwards flag a call by ONE rule.  One element of grad_out is +-inf,
+    NaN or 3.3e38 (above the 3.0e38 threshold): every element of the scattered gradient is NaN (warp: grad_flo too;
+    on-demand: dfmap2 after finish).  3.0e38 itself is not flagged: every output finite, two runs the same bits.
+    Warp / Resample2d at (1, 5, 18, 20): partial 16 x 16 window tiles both ways, C no multiple of the four-channel pass.
+    On-demand at D = 8, 6 x 10, 2 levels, radius 1: 15 backward workgroups of four queries.  None is refused.
+    The other inputs: grad_out of order 1 for the warps, 1e-3 for on-demand (the issue's sizes); what a gradient is
+    MULTIPLIED with in fp32 outside the fixed point -- x, in1 (flow gradients), fmap1, fmap2 (dfmap2's addends, dfmap1's
+    chains) -- of order 1e-3, so that 3.0e38 times it stays far below FLT_MAX and a non-finite output can only come from
+    the flag.  On-demand's bound M = 2 * 3.3e38 * max|fmap1| / sqrt(8) is about 1e36: finite in double."""
+    flagged = not abs(special) <= 3.0e38
+    gen = torch.Generator().manual_seed(17)
+    B, C, H, W = 1, 5, 18, 20
+    x = (1e-3 * torch.randn(B, C, H, W, generator=gen)).to(DEV)
+    flo = (1.5 * torch.randn(B, 2, H, W, generator=gen)).to(DEV)
+    go = torch.randn(B, C, H, W, generator=gen).to(DEV)
+    go[0, 3, 9, 11] = special
+    D, h, w, levels, r = 8, 6, 10, 2, 1
+    f1 = (1e-3 * torch.randn(1, D, h, w, generator=gen)).to(DEV)
+    f2 = (1e-3 * torch.randn(1, D, h, w, generator=gen)).to(DEV)
+    coords = (_grid(1, h, w) + 0.7 * torch.randn(1, 2, h, w, generator=gen)).to(DEV)
+    god = (1e-3 * torch.randn(1, levels * (2 * r + 1) ** 2, h, w, generator=gen)).to(DEV)
+    god[0, 4, 3, 5] = special
+
+    def run():
+        xr, fr = x.clone().requires_grad_(True), flo.clone().requires_grad_(True)
+        warp = torch.autograd.grad(hip_ops.pwc_warp(xr, fr, deterministic=True), (xr, fr), go)
+        res = torch.autograd.grad(hip_ops.resample2d_det(xr, fr), (xr, fr), go)
+        a, b = f1.clone().requires_grad_(True), f2.clone().requires_grad_(True)
+        od = torch.autograd.grad(hip_ops.OnDemandCorrBlock(a, b, num_levels=levels, radius=r)(coords), (a, b), god)
+        return {"warp grad_x": warp[0], "warp grad_flo": warp[1], "resample2d grad_in1": res[0],
+                "resample2d grad_flow": res[1], "ondemand dfmap1": od[0], "ondemand dfmap2": od[1]}
+
+    first = run()
+    if flagged:
+        for k in ("warp grad_x", "warp grad_flo", "resample2d grad_in1", "ondemand dfmap2"):
+            assert bool(torch.isnan(first[k]).all()), k
+    else:
+        second = run()
+        for k, v in first.items():
+            assert bool(torch.isfinite(v).all()), k
+            assert torch.equal(v.view(torch.int32), second[k].view(torch.int32)), k
+
+
 def test_pwc_warp_scatter_through_lds_window_moves_no_bit():
     """The deterministic warp backward scatters through a per-workgroup LDS window (r04: 123 -> 28 us on the 32 x 96 x 320
     level); PCFA_WARP_SCATTER=global is the r03 form, one global atomic per tap.  Both add the same fixed-point integers,
