@@ -26,7 +26,8 @@ import torch.nn.functional as F
 
 from pcfa_amd import _hip
 from tests import winograd as wg
-from tests.fenced import (DEV, NAN_BITS, PCFA_ERR_INVALID_ARG, SENTINEL, TINY, U, Fenced, gamma, stream)
+from tests.fenced import DEV, NAN_BITS, PCFA_ERR_INVALID_ARG, SENTINEL, Fenced, stream
+from tests.gates import dense_stride as _dense_stride, gates, unchanged as _unchanged
 
 pytestmark = pytest.mark.gpu
 torch.set_num_threads(min(16, torch.get_num_threads()))
@@ -38,18 +39,6 @@ def _lib():
     return _hip.load()
 
 
-def _dense_stride(shape):
-    st, acc = [], 1
-    for s in reversed(shape):
-        st.append(acc)
-        acc *= s
-    return tuple(reversed(st))
-
-
-def _unchanged(f):
-    return torch.equal(f.buf.view(torch.int32), f.bits0)
-
-
 def _mask_tensor(shape, gen):
     """negative values, +0.0, -0.0, positive subnormals and positive normals (reference: mask > 0)"""
     m = torch.randn(*shape, generator=gen)
@@ -58,33 +47,6 @@ def _mask_tensor(shape, gen):
     m = torch.where(sel == 2, torch.full((), -0.0), m)
     m = torch.where(sel == 3, torch.full((), 2.0 ** -140), m)
     return m
-
-
-# --------------------------------------------------------------------------- gates
-def gates(got, want, P, n, emu, m, record, prefix=""):
-    """(elementwise ratio, statistical ratio) over every group; records both and returns them."""
-    got = got.double()
-    bound = 2 * gamma(n + 2) * P + (n + 2) * TINY
-    elem = float(((got - want).abs() / bound).max())
-    groups = {"all": (slice(None), slice(None))}
-    H, W = want.shape[-2:]
-    groups.update(wg.regions(H, W, m))
-    stat, worst = 0.0, ""
-    views = [(name, (slice(None), slice(None)) + sl) for name, sl in groups.items()]
-    views += [("ch%d" % c, (slice(None), slice(c, c + 32))) for c in range(0, want.shape[1], 32)]
-    for name, idx in views:
-        w_, g_, e_ = want[idx], got[idx], emu[idx]
-        if w_.numel() < 256 or float(w_.norm()) == 0.0:
-            continue
-        r = wg.rel_l2_64(g_, w_) / (3 * max(wg.rel_l2_64(e_, w_), U))
-        if r > stat:
-            stat, worst = r, name
-    record(prefix + "elem_ratio", "%.3g" % elem)
-    record(prefix + "stat_ratio", "%.3g" % stat)
-    record(prefix + "stat_worst_group", worst)
-    assert elem <= 1, ("elementwise", elem)
-    assert stat <= 1, ("statistical", stat, worst)
-    return elem, stat
 
 
 def epilogue(pre, bias, act, mask, mslope, addend, mask_channels, P=None):
