@@ -190,6 +190,31 @@ PCFA_API int pcfa_softmax_rows_fwd(const float* x, float* y, long long rows, int
 PCFA_API int pcfa_softmax_rows_bwd(const float* y, const float* grad_y, float* grad_x, long long rows, int cols,
                           void* stream);
 
+/* GMA attention without the [N][N] matrix (Config.gma_attention = "streamed"; gma_attn_stream.hip).  q, k, v, g, out,
+ * dv, dq, dk: [BH][N][d], d contiguous, BH = batch * heads; lse, delta: [BH][N]; G, V of dqk: [BH][N][n*d] (the n
+ * iterations' g_i / v_i side by side).  d = 128 only (PCFA_ERR_UNSUPPORTED otherwise).  With s_ij = scale * <q_i, k_j>
+ * (exact fp32 products on the matrix cores, rounded once after the scaling) and P_ij = exp(s_ij - lse_i):
+ *   lse  : lse_i = m_i + log sum_j exp(s_ij - m_i), m_i = max_j s_ij          once per forward, keys ascending
+ *   fwd  : out_i = sum_j P_ij v_j                                              per query block, keys ascending
+ *   dv   : dv_j  = sum_i P_ij g_i                                              per key block, queries ascending
+ *   delta: delta[row] (+)= sum_c g[row][c] out[row][c]   ([rows][d], any d; accumulate = 0 starts the sum)
+ *   dqk  : dS = P o (G V^T - delta), dq = scale * dS k, dk = scale * dS^T q    summed over the n iterations in ONE pass
+ *          each (delta = sum_i <g_i, out_i>); dq or dk may be NULL (not computed)
+ * exp is the device expf of the HIP math library (within 1 ulp), the one pcfa_softmax_rows_fwd uses; the subtraction of
+ * lse / m keeps logits far above 88 from overflowing.  Rows past N in the last block contribute exactly 0.  Fixed
+ * summation order, no atomics: two runs give equal bits.  Offsets are 64-bit; no index of size N^2 exists. */
+PCFA_API int pcfa_attn_stream_lse(const float* q, const float* k, float* lse, int BH, int N, int d, float scale,
+                         void* stream);
+PCFA_API int pcfa_attn_stream_fwd(const float* q, const float* k, const float* v, const float* lse, float* out, int BH,
+                         int N, int d, float scale, void* stream);
+PCFA_API int pcfa_attn_stream_dv(const float* q, const float* k, const float* g, const float* lse, float* dv, int BH,
+                        int N, int d, float scale, void* stream);
+PCFA_API int pcfa_attn_stream_delta(const float* g, const float* out, float* delta, long long rows, int d,
+                           int accumulate, void* stream);
+PCFA_API int pcfa_attn_stream_dqk(const float* q, const float* k, const float* lse, const float* G, const float* V,
+                         const float* delta, float* dq, float* dk, int BH, int N, int d, int n, float scale,
+                         void* stream);
+
 /* Lookup fused with the motion encoder's first layer:
  *   out = relu?(convc1(CorrBlock.__call__(coords)))   models/raft/corr.py:29-50 feeding models/raft/update.py:79-93
  *   (convc1 = Conv2d(4*81, 256, 1)); identical in models/gma.

@@ -54,6 +54,11 @@ SIGNATURES = {
                               c_longlong, c_longlong, c_longlong, c_float, c_int, _P, c_size_t, _P]),
     "pcfa_softmax_rows_fwd": (c_int, [_P, _P, c_longlong, c_int, _P]),
     "pcfa_softmax_rows_bwd": (c_int, [_P, _P, _P, c_longlong, c_int, _P]),
+    "pcfa_attn_stream_lse": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, _P]),
+    "pcfa_attn_stream_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, _P]),
+    "pcfa_attn_stream_dv": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, _P]),
+    "pcfa_attn_stream_delta": (c_int, [_P, _P, _P, c_longlong, c_int, c_int, _P]),
+    "pcfa_attn_stream_dqk": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
     "pcfa_lookup_convc1_packed_floats": (c_longlong, [c_int]),
     "pcfa_lookup_convc1_pack_weights": (c_int, [_P, _P, c_int, c_int, _P]),
     "pcfa_lookup_convc1_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),

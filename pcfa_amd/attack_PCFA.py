@@ -493,7 +493,8 @@ class PairsInFlight:
         process is captured by ONE host thread, i.e. with one rocBLAS handle, and a handle owns ONE device workspace that
         all its launches share in stream order -- replayed side by side, two lanes' products use it at the same time.
         Observed (r05, tools/dev/flight_scaling.py GMA 436x1024, two lanes): the first step never returns.  The package's own
-        products take their split-K scratch from the caller, so the build with gma_gemm = "hip" is safe in flight; likewise
+        products take their split-K scratch from the caller, so the build with gma_gemm = "hip" is safe in flight, and so is
+        gma_attention = "streamed" (own kernels, no scratch at all) whatever gma_gemm says; likewise
         SpyNet with spynet_ops = "hip" (own 7x7 convolutions and warp, no scratch shared between lanes) and FlowNet2 with
         flownet2_ops = "hip" (own strided / transposed convolutions, no library kernel in the closure)."""
         net = getattr(getattr(attack, "args", None), "net", None)
@@ -508,6 +509,8 @@ class PairsInFlight:
             raise ValueError("SpyNet with Config.spynet_ops='lib' keeps library convolutions inside its captured closure and "
                              "cannot run several pairs in flight: build the model with spynet_ops='hip' "
                              "(PCFA_SPYNET_OPS=hip) or use --pairs_in_flight 1")
+        if net == "GMA" and config.cfg(attack.model).gma_attention == "streamed":
+            return   # no attention product goes to rocBLAS, and the streamed kernels take no scratch shared between lanes
         if net == "GMA" and config.cfg(attack.model).gma_gemm != "hip":
             raise ValueError("GMA with Config.gma_gemm='lib' cannot run several pairs in flight (the lanes' captured rocBLAS "
                              "products would share one handle's workspace): build the model with gma_gemm='hip' "

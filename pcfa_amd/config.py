@@ -28,6 +28,8 @@ class Config:
     defer_relu: bool = True              # ReLU backward of single-consumer layers inside neighbouring kernels
     pyramid_bwd_windows: bool = True     # pyramid backward over the lookup windows only (False: dense products)
     gma_gemm: str = "lib"                # GMA attention products: "lib" (rocBLAS through torch.matmul) | "hip" (pcfa_gemm_f32)
+    gma_attention: str = "materialised"  # GMA attention: "materialised" ([N, N] softmax matrix, products per gma_gemm) | "streamed"
+                                         # (ops.streamed_attention: tiles recomputed per pass, O(N*d) memory, no library product)
     conv1x1: str = "lib"                 # the encoders' output layer and the mask head's 1x1 layer: "lib" | "hip" (pcfa_gemm_f32:
                                          # a RAFT closure then holds no library kernel at all)
     corr: str = "all_pairs"              # correlation: "all_pairs" (CorrBlock: O(Q^2) pyramid, fused lookup -> convc1) |
@@ -58,6 +60,7 @@ class Config:
                    overlap_encoders=_env_bool("PCFA_OVERLAP_ENCODERS", False),
                    defer_relu=_env_bool("PCFA_DEFER_RELU", True),
                    gma_gemm=os.environ.get("PCFA_GMA_GEMM", "lib"),
+                   gma_attention=os.environ.get("PCFA_GMA_ATTENTION", "materialised"),
                    conv1x1=os.environ.get("PCFA_CONV1X1", "lib"),
                    corr=os.environ.get("PCFA_CORR", "all_pairs"),
                    spynet_ops=os.environ.get("PCFA_SPYNET_OPS", "lib"),
@@ -67,6 +70,8 @@ class Config:
     def __post_init__(self):
         if self.gma_gemm not in ("lib", "hip"):
             raise ValueError("Config.gma_gemm must be 'lib' or 'hip', got %r" % (self.gma_gemm,))
+        if self.gma_attention not in ("materialised", "streamed"):
+            raise ValueError("Config.gma_attention must be 'materialised' or 'streamed', got %r" % (self.gma_attention,))
         if self.conv1x1 not in ("lib", "hip"):
             raise ValueError("Config.conv1x1 must be 'lib' or 'hip', got %r" % (self.conv1x1,))
         if self.corr not in ("all_pairs", "on_demand"):

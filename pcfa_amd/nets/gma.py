@@ -6,7 +6,8 @@ Behavioural reference (cv-stuttgart/PCFA):
     models/gma/update.py:112-139     GMAUpdateBlock
     models/gma/corr.py:15-63         -> pcfa_amd.ops.get().CorrBlock (same HIP kernels as RAFT)
                                         or OnDemandCorrBlock under Config.corr = "on_demand" (O(Q*D) memory;
-                                        the attention stays O(Q^2), and in flight GMA still needs gma_gemm = "hip")
+                                        the attention stays O(Q^2) unless Config.gma_attention = "streamed":
+                                        ops.streamed_attention, O(Q*d), no library product, allowed in flight)
 
 Parameter names follow the public gma-sintel.pth checkpoint.  The reference
 config enables fp16 autocast on CUDA (models/_config/gma_config.json:5); the CPU
@@ -57,8 +58,15 @@ class Attention(nn.Module):
         q = q.reshape(b, heads, -1, h * w).transpose(-1, -2)
         k = k.reshape(b, heads, -1, h * w).transpose(-1, -2)
         o = ops.get()
-        if (hasattr(o, "attention_softmax") and not getattr(self.args, "position_only", False)
-                and not getattr(self.args, "position_and_content", False)):
+        positional = getattr(self.args, "position_only", False) or getattr(self.args, "position_and_content", False)
+        if cfg(self).gma_attention == "streamed":
+            if positional:
+                raise ValueError("Config.gma_attention='streamed' serves the content-only attention: position_only / "
+                                 "position_and_content need the materialised [N, N] scores")
+            if hasattr(o, "streamed_attention"):
+                # a handle instead of the [N, N] matrix: Aggregate multiplies it tile by tile (gma_gemm has no say here)
+                return o.streamed_attention(q.contiguous(), k.contiguous(), self.scale)
+        if hasattr(o, "attention_softmax") and not positional:
             # similarity product on the fp32 matrix cores, row softmax with one read + one write of the [N, N] matrix
             # (pcfa_gemm_f32 + pcfa_softmax_rows_*); scale applied to the product instead of to q (gma.py:59)
             return o.attention_softmax(q.contiguous(), k.contiguous(), self.scale, gemm=cfg(self).gma_gemm)
@@ -130,7 +138,9 @@ class Aggregate(nn.Module):
         heads = self.heads
         v = self.to_v(fmap).reshape(b, heads, -1, h * w).transpose(-1, -2)  # b h (x y) d
         o = ops.get()
-        if shared is not None and torch.is_grad_enabled() and attn.requires_grad:
+        if hasattr(o, "StreamedAttention") and isinstance(attn, o.StreamedAttention):
+            out = o.streamed_attn_times_value(attn, v)                       # b h (x y) d, no [N, N] matrix
+        elif shared is not None and torch.is_grad_enabled() and attn.requires_grad:
             if hasattr(o, "AttnGradShare") and isinstance(shared, o.AttnGradShare):
                 out = o.attn_times_value(attn, v, shared)                    # b h (x y) d, hand-written GEMM path
             else:
@@ -192,7 +202,7 @@ class RAFTGMA(nn.Module):
         hdim, cdim = self.hidden_dim, self.context_dim
 
         fmap1, fmap2 = self.fnet(images12, split=image1.shape[0])
-        if cfg(self).corr == "on_demand":   # O(Q*D) correlation; the attention below stays O(Q^2)
+        if cfg(self).corr == "on_demand":   # O(Q*D) correlation; the attention below is O(Q^2) unless gma_attention = "streamed"
             corr_fn = ops.get().OnDemandCorrBlock(_f32(fmap1), _f32(fmap2), num_levels=4, radius=self.args.corr_radius)
         else:
             corr_fn = ops.get().CorrBlock(_f32(fmap1), _f32(fmap2), num_levels=4, radius=self.args.corr_radius,

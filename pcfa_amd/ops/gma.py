@@ -1,5 +1,6 @@
 """GMA attention (models/gma/gma.py:34-77,79-115): row softmax in one pass, attention products,
-the shared attention gradient; pcfa_gemm_f32."""
+the shared attention gradient; pcfa_gemm_f32.  And the same attention without the [N, N] matrix (Config.gma_attention =
+"streamed"): streamed_attention / streamed_attn_times_value on pcfa_attn_stream_*."""
 import ctypes
 import os
 import weakref
@@ -135,3 +136,102 @@ class _AttnTimesValue(torch.autograd.Function):
 
 def attn_times_value(attn, v, shared):
     return _AttnTimesValue.apply(attn, v, shared)
+
+
+# --------------------------------------------------------------------------- #
+# The same attention without the [N, N] matrix (Config.gma_attention = "streamed"; csrc/gma_attn_stream.hip)
+# --------------------------------------------------------------------------- #
+class StreamedAttention:
+    """Handle of softmax(scale * q k^T) that never forms the matrix: q, k [.., N, 128], the scale and the row statistics
+    lse [.., N], computed once on first use (the attention depends on the context features only, so every refinement
+    iteration shares them).  It also carries what AttnGradShare carries: the nodes of the iterations park (g_i, v_i) and
+    add their <g_i, out_i> to delta; whichever runs last makes ONE pcfa_attn_stream_dqk pass over all of them."""
+
+    def __init__(self, q, k, scale):
+        _dev(q, k)
+        if q.shape != k.shape:
+            raise ValueError("streamed_attention: q %s and k %s differ in shape" % (tuple(q.shape), tuple(k.shape)))
+        self.q, self.k, self.scale = q.contiguous(), k.contiguous(), float(scale)
+        self.N, self.d = q.shape[-2], q.shape[-1]
+        self.BH = q.numel() // (self.N * self.d)
+        self._lse = None
+        self.pending = 0
+        self.gs, self.vs, self.delta = [], [], None
+
+    def lse(self):
+        if self._lse is None:
+            q, k = self.q.detach(), self.k.detach()
+            lse = torch.empty(q.shape[:-1], device=q.device, dtype=torch.float32)
+            _call("pcfa_attn_stream_lse", _ptr(q), _ptr(k), _ptr(lse), self.BH, self.N, self.d, self.scale)
+            self._lse = lse
+        return self._lse
+
+
+def streamed_attention(q, k, scale):
+    """The handle of softmax(scale * q k^T, dim=-1) for q, k [.., N, 128]; multiply it with streamed_attn_times_value."""
+    return StreamedAttention(q, k, scale)
+
+
+def _stream_fwd(h, q, k, v):
+    out = torch.empty_like(v)
+    _call("pcfa_attn_stream_fwd", _ptr(q), _ptr(k), _ptr(v), _ptr(h.lse()), _ptr(out), h.BH, h.N, h.d, h.scale)
+    return out
+
+
+class _StreamedAttnTimesValue(torch.autograd.Function):
+    """out_i = softmax(scale q k^T) v_i, one node per refinement iteration, inputs (q, k, v_i).  Saves v_i and out_i
+    ([N, 128] each).  Backward: dv_i = P^T g_i at once; (g_i, v_i) are parked and delta += <g_i, out_i>; the node that
+    runs last returns dq, dk from one pass over dS = P o ([g_1|..|g_n] [v_1|..|v_n]^T - delta), the others None."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, h):
+        v = v.contiguous()
+        out = _stream_fwd(h, q, k, v)
+        ctx.save_for_backward(q, k, v, out)
+        ctx.h = h
+        h.pending += 1
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        q, k, v, out = ctx.saved_tensors
+        h = ctx.h
+        g = g.contiguous()
+        dv = None
+        if ctx.needs_input_grad[2]:
+            dv = torch.empty_like(v)
+            _call("pcfa_attn_stream_dv", _ptr(q), _ptr(k), _ptr(g), _ptr(h.lse()), _ptr(dv), h.BH, h.N, h.d, h.scale)
+        dq = dk = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            if h.pending <= 0:
+                raise RuntimeError("GMA attention gradient: backward re-entered after the shared buffers were released; "
+                                   "run a fresh forward (retain_graph is not supported on this path)")
+            first = h.delta is None
+            if first:
+                h.delta = torch.empty(q.shape[:-1], device=q.device, dtype=torch.float32)
+            _call("pcfa_attn_stream_delta", _ptr(g), _ptr(out), _ptr(h.delta), h.BH * h.N, h.d, 0 if first else 1)
+            h.gs.append(g)
+            h.vs.append(v)
+            h.pending -= 1
+            if h.pending == 0:
+                n = len(h.gs)
+                gcat = h.gs[0] if n == 1 else torch.cat(h.gs, dim=-1)
+                vcat = h.vs[0] if n == 1 else torch.cat(h.vs, dim=-1)
+                delta, h.gs, h.vs, h.delta = h.delta, [], [], None
+                dq = torch.empty_like(q) if ctx.needs_input_grad[0] else None
+                dk = torch.empty_like(k) if ctx.needs_input_grad[1] else None
+                _call("pcfa_attn_stream_dqk", _ptr(q), _ptr(k), _ptr(h.lse()), _ptr(gcat), _ptr(vcat), _ptr(delta),
+                      _ptr(dq), _ptr(dk), h.BH, h.N, h.d, n, h.scale)
+        return dq, dk, dv, None
+
+
+def streamed_attn_times_value(handle, v):
+    """softmax(scale q k^T) v for the handle's q, k and v [.., N, 128].  Under no_grad, or when nothing requires a
+    gradient, the same forward kernels run and nothing is saved."""
+    _dev(v)
+    if v.shape != handle.q.shape:
+        raise ValueError("streamed_attn_times_value: v %s does not match q %s" % (tuple(v.shape), tuple(handle.q.shape)))
+    if not (torch.is_grad_enabled() and (handle.q.requires_grad or handle.k.requires_grad or v.requires_grad)):
+        return _stream_fwd(handle, handle.q.detach(), handle.k.detach(), v.detach().contiguous())
+    return _StreamedAttnTimesValue.apply(handle.q, handle.k, v, handle)
