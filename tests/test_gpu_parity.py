@@ -244,9 +244,11 @@ def test_corr_block_edge_cases():
 @pytest.mark.parametrize("shape", [(1, 64, 16, 20), (2, 32, 23, 37), (1, 256, 55, 128)])
 def test_lookup_convc1_fused_vs_unfused_and_oracle(oracle_ops, shape):
     """pcfa_lookup_convc1_fwd / _bwd (lookup -> convc1 -> ReLU in one launch per direction, reference
-    models/raft/corr.py:29-50 + update.py:79-93) against (a) the un-fused HIP path lookup + F.conv2d (same taps bit for
-    bit, so only the fp32 summation order of the 324-term dot product differs: 1e-5 of the output range, gradients 2e-5
-    relative L2) and (b) the oracle on CPU.  Queries not a multiple of 32, two images, coordinates far outside."""
+    models/raft/corr.py:29-50 + update.py:79-93) against (a) the un-fused HIP path lookup + F.conv2d (the same taps up to
+    one rounding -- hipcc contracts the blend's first two products the other way round in the two kernels,
+    tests/test_lookup_f64_gpu.py::test_convc1_selects_taps -- and another fp32 summation order of the 324-term dot
+    product: 1e-5 of the output range, gradients 2e-5 relative L2) and (b) the oracle on CPU.  Queries not a multiple of
+    32, two images, coordinates far outside."""
     import torch.nn.functional as F
     B, D, H, W = shape
     gen = torch.Generator().manual_seed(H + W)
