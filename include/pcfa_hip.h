@@ -186,6 +186,25 @@ PCFA_API size_t pcfa_gemm_f32_workspace_bytes(int M, int N, int batch, int split
 PCFA_API int pcfa_gemm_f32(const float* A, const float* B, float* C, int M, int N, int K, long long lda, long long ldb,
                   long long ldc, int a_kmajor, int b_kmajor, int batch, long long bsA, long long bsB, long long bsC,
                   float alpha, int splits, void* workspace, size_t workspace_bytes, void* stream);
+/* The same two contracts on the bf16 matrix cores with fp32 accuracy (Config.mfma = "bf16x3"; gemm_bf16x3.hip): argument
+ * lists, layouts, error codes, split-K workspace and ordered reduction of pcfa_gemm_f32, and the `pyr` layout and
+ * 1/sqrt(D) of pcfa_corr_pyramid_fwd.  Every fp32 operand is split into three round-to-nearest bf16 pieces,
+ * a = a0 + a1 + a2 exactly, on its way into LDS; the six products a_i b_j with i + j <= 2 run on
+ * v_mfma_f32_32x32x16_bf16 (exact products, fp32 accumulation) at 16/6 of the fp32 matrix rate.  Fixed summation order,
+ * no atomics: two calls give equal bits.  (These entry points were added without a change of PCFA_ABI_VERSION, like
+ * every addition before them: the version changes when an existing declaration does.)
+ * Element bound, u = 2^-24, gamma(n) = n u / (1 - n u), n6 = 6 K + splits + 8:
+ *   |C - alpha A B| <= 2 gamma(n6) |alpha| (|A| |B|) + u |alpha| (|A| |B|) + 6 K 2^-126
+ * -- the first term for the accumulation in any order, the second for the three dropped products a1 b2, a2 b1, a2 b2
+ * (at most 3.32 * 2^-26 |a b| each).  Statistically it passes the fp32 core's own gate, rel-L2 <= 2 u sqrt(K + splits + 2).
+ * Range: |x| >= 2^127 rounds a0 to infinity; a non-finite operand gives a non-finite output in its row / column of C,
+ * not necessarily of the same class (inf - inf in the split makes a +inf operand a NaN result). */
+PCFA_API size_t pcfa_gemm_bf16x3_workspace_bytes(int M, int N, int batch, int splits);
+PCFA_API int pcfa_gemm_bf16x3(const float* A, const float* B, float* C, int M, int N, int K, long long lda,
+                     long long ldb, long long ldc, int a_kmajor, int b_kmajor, int batch, long long bsA, long long bsB,
+                     long long bsC, float alpha, int splits, void* workspace, size_t workspace_bytes, void* stream);
+PCFA_API int pcfa_corr_pyramid_fwd_bf16x3(const float* fmap1, const float* f2ext, float* pyr, int B, int D, int H,
+                                 int W, int num_levels, void* stream);
 PCFA_API int pcfa_softmax_rows_fwd(const float* x, float* y, long long rows, int cols, void* stream);
 PCFA_API int pcfa_softmax_rows_bwd(const float* y, const float* grad_y, float* grad_x, long long rows, int cols,
                           void* stream);

@@ -52,6 +52,10 @@ SIGNATURES = {
     "pcfa_gemm_f32_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "pcfa_gemm_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong, c_int, c_int, c_int,
                               c_longlong, c_longlong, c_longlong, c_float, c_int, _P, c_size_t, _P]),
+    "pcfa_gemm_bf16x3_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "pcfa_gemm_bf16x3": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong, c_int, c_int,
+                                 c_int, c_longlong, c_longlong, c_longlong, c_float, c_int, _P, c_size_t, _P]),
+    "pcfa_corr_pyramid_fwd_bf16x3": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "pcfa_softmax_rows_fwd": (c_int, [_P, _P, c_longlong, c_int, _P]),
     "pcfa_softmax_rows_bwd": (c_int, [_P, _P, _P, c_longlong, c_int, _P]),
     "pcfa_attn_stream_lse": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_float, _P]),

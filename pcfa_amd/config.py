@@ -3,7 +3,7 @@
 `import_and_load(..., config=Config(...))` attaches the object to every sub-module of the network it builds
 (`attach(model, cfg)`); the networks read `cfg(self).<switch>` and hand operator-level switches to the operator table as
 keyword arguments (`CorrBlock(..., bwd_windows=...)`, `pwc_warp(..., deterministic=...)`, `dense_block(..., fused_masks=...)`,
-`attention_softmax(..., gemm=...)`).  Nothing flips a module global after import: an A/B run builds a second model (the
+`attention_softmax(..., gemm=..., mfma=...)`).  Nothing flips a module global after import: an A/B run builds a second model (the
 weights are seeded, the packs are cached per tensor) with `dataclasses.replace(DEFAULT, switch=value)`.
 
 Every switch selects between two executions of the same arithmetic (parity-tested against each other); the defaults are
@@ -34,6 +34,12 @@ class Config:
                                          # a RAFT closure then holds no library kernel at all)
     corr: str = "all_pairs"              # correlation: "all_pairs" (CorrBlock: O(Q^2) pyramid, fused lookup -> convc1) |
                                          # "on_demand" (OnDemandCorrBlock: window dot products per lookup, O(Q*D) memory)
+    mfma: str = "f32"                    # arithmetic of the hand-written GEMM core: "f32" (v_mfma_f32_32x32x2_f32) | "bf16x3" (each
+                                         # fp32 operand split into three bf16 pieces, six v_mfma_f32_32x32x16_bf16 products: fp32
+                                         # accuracy at 16/6 of the fp32 matrix roof).  Takes effect where that core runs: the
+                                         # all-pairs pyramid forward (always), the attention products under gma_gemm="hip", the
+                                         # 1x1 layers under conv1x1="hip".  Stay fp32: the pyramid backward (sparse-window
+                                         # products, pooling adjoint), corr="on_demand", gma_attention="streamed"
     # ---- PWC-Net (nets/pwcnet.py) ----
     dilated_as_subgrids: tuple = (2, 4, 8, 16)   # dilations run as d*d plain 3x3 convolutions on sub-grids (() = library)
     deconv_fewout: bool = True           # deconv / upfeat layers and the x4 up-sampling on own deterministic kernels
@@ -63,6 +69,7 @@ class Config:
                    gma_attention=os.environ.get("PCFA_GMA_ATTENTION", "materialised"),
                    conv1x1=os.environ.get("PCFA_CONV1X1", "lib"),
                    corr=os.environ.get("PCFA_CORR", "all_pairs"),
+                   mfma=os.environ.get("PCFA_MFMA", "f32"),
                    spynet_ops=os.environ.get("PCFA_SPYNET_OPS", "lib"),
                    flownet2_ops=os.environ.get("PCFA_FLOWNET2_OPS", "lib"),
                    max_cached_shapes=int(os.environ.get("PCFA_MAX_CACHED_SHAPES", "4")))
@@ -76,6 +83,8 @@ class Config:
             raise ValueError("Config.conv1x1 must be 'lib' or 'hip', got %r" % (self.conv1x1,))
         if self.corr not in ("all_pairs", "on_demand"):
             raise ValueError("Config.corr must be 'all_pairs' or 'on_demand', got %r" % (self.corr,))
+        if self.mfma not in ("f32", "bf16x3"):
+            raise ValueError("Config.mfma must be 'f32' or 'bf16x3', got %r" % (self.mfma,))
         if self.spynet_ops not in ("lib", "hip"):
             raise ValueError("Config.spynet_ops must be 'lib' or 'hip', got %r" % (self.spynet_ops,))
         if self.flownet2_ops not in ("lib", "hip"):

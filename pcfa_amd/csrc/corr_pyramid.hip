@@ -16,10 +16,9 @@
 // v_mfma_f32_32x32x2_f32 (exact fp32, k-ordered fma chain), LDS double buffer
 // fed by register prefetch.
 #include "common.hpp"
+#include "gemm_tile.hpp"   // block tile, PoolArgs, the epilogues, the split-K reduction
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #ifndef PCFA_GEMM_BK
 #define PCFA_GEMM_BK 16
@@ -30,7 +29,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #ifndef PCFA_GEMM_STORE_MID_AT
 #define PCFA_GEMM_STORE_MID_AT 4
 #endif
-constexpr int BM = 128, BN = 128, BK = PCFA_GEMM_BK;
+constexpr int BK = PCFA_GEMM_BK;
 constexpr int NLD = BK / 8;   // float4 per thread and operand tile (128 x BK floats over 256 threads)
 constexpr int KV = BK / 4;    // float4 per row of a k-contiguous operand tile
 constexpr int LDS_KM = 132;  // row stride (floats) when the operand arrives k-major (b128 writes)
@@ -141,21 +140,8 @@ __device__ __forceinline__ void tile_store(float* __restrict__ s, const float4 (
 
 // C[m][n] = (sum_k A(m,k) B(k,n)) / div   over k in this block's split.
 // grid = (ceil(N/128), ceil(M/128), batch*splits).
-// POOL (correlation pyramid forward only): the GEMM runs over the level-0 columns [0, S0) and the tail columns
-// [off_tail, slab) (levels >= 3 and the zero tile, taken from f2ext as before); levels 1 and 2 are average-pooled from
-// the level-0 accumulators in the epilogue, the way the reference pools the correlation volume
-// (models/raft/corr.py:24-27: F.avg_pool2d of the level below) -- 24 % fewer MFMAs than multiplying against the
-// pooled copies of fmap2, and the pooled values round like the reference's.  Needs W % 16 == 0 (no x padding inside
-// the tiles of levels 1 and 2) and L >= 3; the caller checks.
-struct PoolArgs {
-  int nb0;        // N-blocks (of BN columns) covering the level-0 columns
-  int S0;         // level-0 columns (tiles x 16)
-  int off_tail;   // first tail column
-  int tw0, tiles0;
-  int off1, tw1, h1, w1;
-  int off2, tw2, h2, w2;
-};
-constexpr int SC = BN + 4;   // row stride of the epilogue image of the C tile
+// POOL (correlation pyramid forward only; PoolArgs and the pooled epilogue: gemm_tile.hpp): levels 1 and 2 are
+// average-pooled from the level-0 accumulators in the epilogue.
 
 // UNPOOL (correlation pyramid backward only, 4 levels, W % 16 == 0): the transposed form of POOL.  The gradient of the
 // reference's volume is g0 + up(g1 + up(g2 + up(g3)/4)/4)/4 (autograd of three F.avg_pool2d, models/raft/corr.py:24-27)
@@ -244,19 +230,8 @@ __device__ __forceinline__ void gemm_f32_mfma_body(
   C += batch * bsC + split * ssC;
   int kbeg = split * kchunk;
   const int kend = SPARSE ? K : min(K, kbeg + kchunk);
-  // XCD-aware tile order (cdna_hip_programming.md T1, bijective form): workgroups are dealt round-robin over the 8
-  // XCDs, so consecutive linear ids land on different L2s; remapped, every XCD walks a contiguous band of tile rows
-  // and re-reads its A band / the streamed B tiles from its own L2.  Speed only -- any placement is correct.
   int by = blockIdx.y, bx = blockIdx.x;
-#ifndef PCFA_GEMM_NO_XCD
-  {
-    const int nx = gridDim.x, nwg = nx * gridDim.y;
-    const int orig = by * nx + bx, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-    const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-    by = wg / nx;
-    bx = wg - by * nx;
-  }
-#endif
+  gemm_tile_xcd_order(by, bx);
   const int m0 = by * BM;
   int n0 = bx * BN;
   bool pooled = false;
@@ -376,77 +351,7 @@ __device__ __forceinline__ void gemm_f32_mfma_body(
     cur ^= 1;
   }
 
-  // Epilogue: C/D map of 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).
-  // The reference divides by sqrt(D); when that is a power of two (D = 256 -> 16) multiplying by its reciprocal
-  // is the same fp32 result and saves a division sequence per output element.
-  int dexp;
-  const bool pow2 = frexpf(div, &dexp) == 0.5f;
-  const float rdiv = 1.0f / div;
-  if (POOL && pooled) {
-    // ---- C tile -> LDS (the stage buffers are free: the loop ended on a barrier) ----
-    float* sC = smem;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          sC[row * SC + wc * 64 + j * 32 + l31] = pow2 ? acc[i][j][r] * rdiv : acc[i][j][r] / div;
-        }
-    __syncthreads();
-    const int tid = threadIdx.x;
-    // level 0: rows of 512 B, 16-B stores
-#pragma unroll
-    for (int k = 0; k < BM * BN / 4 / 256; ++k) {
-      const int idx = tid + 256 * k, row = idx >> 5, c4 = (idx & 31) * 4;
-      if (m0 + row < M && n0 + c4 < N)
-        *reinterpret_cast<float4*>(&C[(long long)(m0 + row) * ldc + n0 + c4]) =
-            *reinterpret_cast<const float4*>(&sC[row * SC + c4]);
-    }
-    // levels 1 and 2: thread = (query row, 4x4 tile); sums in avg_pool2d's window order, one division by 4 each
-#pragma unroll
-    for (int k = 0; k < BM * (BN / 16) / 256; ++k) {
-      const int item = tid + 256 * k, row = item >> 3, t = item & 7;
-      const int T0 = n0 / 16 + t;
-      if (m0 + row >= M || T0 >= pool.tiles0) continue;
-      const int ty = T0 / pool.tw0, tx = T0 - ty * pool.tw0;
-      float v[4][4];
-#pragma unroll
-      for (int y = 0; y < 4; ++y) {
-        const float4 q4 = *reinterpret_cast<const float4*>(&sC[row * SC + 16 * t + 4 * y]);
-        v[y][0] = q4.x; v[y][1] = q4.y; v[y][2] = q4.z; v[y][3] = q4.w;
-      }
-      float* crow = C + (long long)(m0 + row) * ldc;
-      float l1[2][2];
-#pragma unroll
-      for (int Y = 0; Y < 2; ++Y) {
-#pragma unroll
-        for (int X = 0; X < 2; ++X) {
-          const float sum = ((v[2 * Y][2 * X] + v[2 * Y][2 * X + 1]) + v[2 * Y + 1][2 * X]) + v[2 * Y + 1][2 * X + 1];
-          l1[Y][X] = (2 * ty + Y < pool.h1 && 2 * tx + X < pool.w1) ? sum * 0.25f : 0.f;
-        }
-        float* d1 = crow + pool.off1 + ((ty >> 1) * pool.tw1 + (tx >> 1)) * 16 + (2 * (ty & 1) + Y) * 4 + 2 * (tx & 1);
-        *reinterpret_cast<float2*>(d1) = make_float2(l1[Y][0], l1[Y][1]);
-      }
-      const float sum2 = ((l1[0][0] + l1[0][1]) + l1[1][0]) + l1[1][1];
-      crow[pool.off2 + ((ty >> 2) * pool.tw2 + (tx >> 2)) * 16 + (ty & 3) * 4 + (tx & 3)] =
-          (ty < pool.h2 && tx < pool.w2) ? sum2 * 0.25f : 0.f;
-    }
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int col = n0 + wc * 64 + j * 32 + l31;
-      if (col >= N) continue;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (row < M) C[(long long)row * ldc + col] = pow2 ? acc[i][j][r] * rdiv : acc[i][j][r] / div;
-      }
-    }
+  gemm_tile_epilogue<POOL>(acc, smem, C, M, N, ldc, m0, n0, div, pooled, pool);
 }
 
 template <bool B_KN>
@@ -497,19 +402,6 @@ __global__ void splitk_reduce_untile_kernel(const float* __restrict__ part, floa
     const long long src = pl * S0 + ((((y >> 2) * tw0 + (x >> 2)) << 4) + ((y & 3) << 2) + (x & 3));
     float s = part[src];
     for (int k = 1; k < splits; ++k) s += part[(long long)k * ss + src];
-    out[i] = s;
-  }
-}
-
-// out[i] = sum_s partial[s][i]  (fixed order -> deterministic).  No scaling:
-// the split GEMMs already divided every partial by sqrt(D).
-__global__ void splitk_reduce_kernel(const float* __restrict__ part, float* __restrict__ out,
-                                     long long n, int splits, long long ss) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) {
-    float s = part[i];
-    for (int k = 1; k < splits; ++k) s += part[(long long)k * ss + i];
     out[i] = s;
   }
 }
@@ -594,8 +486,6 @@ size_t pooled_lds_bytes(const PyrLayout& P) {
   for (int l = 1; l < P.L; ++l) n += (size_t)P.h[l] * P.w[l];
   return n * sizeof(float);
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 constexpr int BWD_SPLITS = 8;
 constexpr int MAX_COORDS = 32;
@@ -765,14 +655,7 @@ extern "C" int pcfa_corr_pyramid_fwd(const float* fmap1, const float* f2ext, flo
   static const bool pool_off = getenv("PCFA_PYRAMID_POOL") && atoi(getenv("PCFA_PYRAMID_POOL")) == 0;   // A/B switch
   if (vecA && vecB && D % 4 == 0 && Q >= 4 && P.L >= 3 && W % 16 == 0 && !pool_off) {
     PoolArgs pa;
-    pa.tw0 = P.tw[0];
-    pa.tiles0 = ((P.h[0] + 3) / 4) * P.tw[0];
-    pa.S0 = pa.tiles0 * 16;
-    pa.nb0 = pcfa_cdiv(pa.S0, BN);
-    pa.off_tail = P.L > 3 ? P.off[3] : P.zero;
-    pa.off1 = P.off[1]; pa.tw1 = P.tw[1]; pa.h1 = P.h[1]; pa.w1 = P.w[1];
-    pa.off2 = P.off[2]; pa.tw2 = P.tw[2]; pa.h2 = P.h[2]; pa.w2 = P.w[2];
-    if (pa.S0 != P.off[1] || pa.off_tail % 16 != 0 || pa.off_tail > S) return PCFA_ERR_UNSUPPORTED;
+    if (!make_pool_args(P, pa)) return PCFA_ERR_UNSUPPORTED;
     dim3 gridp(pa.nb0 + pcfa_cdiv(S - pa.off_tail, BN), pcfa_cdiv(Q, BM), B);
     pcfa_launch(corr_pyramid_pool_gemm_kernel, gridp, dim3(256), 0, (hipStream_t)stream, fmap1, f2ext, pyr, Q, S, D,
                 (long long)Q, (long long)S, (long long)S, (long long)D * Q, (long long)D * S, (long long)Q * S,

@@ -20,7 +20,7 @@ import torch.nn as nn
 from .. import ops
 from ..config import cfg
 from .raft import (BasicEncoder, BasicMotionEncoder, FlowHead, LookupRef, SepConvGRU, _mask_head, convex_upsample,
-                   _f32, coords_grid, mask_logits)
+                   _f32, coords_grid, mask_logits, mfma_kw)
 
 
 class RelPosEmb(nn.Module):
@@ -69,7 +69,8 @@ class Attention(nn.Module):
         if hasattr(o, "attention_softmax") and not positional:
             # similarity product on the fp32 matrix cores, row softmax with one read + one write of the [N, N] matrix
             # (pcfa_gemm_f32 + pcfa_softmax_rows_*); scale applied to the product instead of to q (gma.py:59)
-            return o.attention_softmax(q.contiguous(), k.contiguous(), self.scale, gemm=cfg(self).gma_gemm)
+            return o.attention_softmax(q.contiguous(), k.contiguous(), self.scale, gemm=cfg(self).gma_gemm,
+                                       mfma=cfg(self).mfma)
         q = self.scale * q
         if getattr(self.args, "position_only", False):
             sim = self.pos_emb(q.reshape(b, heads, h, w, -1)).reshape(b, heads, h * w, h * w)
@@ -206,7 +207,7 @@ class RAFTGMA(nn.Module):
             corr_fn = ops.get().OnDemandCorrBlock(_f32(fmap1), _f32(fmap2), num_levels=4, radius=self.args.corr_radius)
         else:
             corr_fn = ops.get().CorrBlock(_f32(fmap1), _f32(fmap2), num_levels=4, radius=self.args.corr_radius,
-                                          bwd_windows=cfg(self).pyramid_bwd_windows)
+                                          bwd_windows=cfg(self).pyramid_bwd_windows, **mfma_kw(cfg(self)))
 
         net, inp = torch.split(self.cnet(image1), [hdim, cdim], dim=1)
         net, inp = torch.tanh(net), torch.relu(inp)
@@ -223,7 +224,7 @@ class RAFTGMA(nn.Module):
         flow_predictions = []
         flow_up = None
         o = ops.get()   # the gradient of `attention` (used `iters` times) is formed once, by the last node that runs
-        attn_grad = o.AttnGradShare(cfg(self).gma_gemm) if hasattr(o, "AttnGradShare") else _SharedAttnGrad()
+        attn_grad = o.AttnGradShare(cfg(self).gma_gemm, cfg(self).mfma) if hasattr(o, "AttnGradShare") else _SharedAttnGrad()
         flow_cur = coords1 - coords0
         for itr in range(iters):
             coords1 = coords1.detach()

@@ -252,11 +252,18 @@ def _is_plain1x1(conv):
             and conv.groups == 1)
 
 
+def mfma_kw(config):
+    """Config.mfma as the operators' keyword.  The default goes without it, so an operator table that implements only the
+    default arithmetic (the CPU oracle of the tests) keeps serving default builds; any other value reaches the operator,
+    which then has to know it."""
+    return {} if config.mfma == "f32" else {"mfma": config.mfma}
+
+
 def _conv1x1(conv, x, config):
     """conv(x) for a 1x1 layer: the library's convolution, or -- Config.conv1x1 = "hip", frozen weights, GPU -- the package's
     own product (ops.conv1x1)."""
     if config.conv1x1 == "hip" and x.is_cuda and _is_plain1x1(conv) and _frozen_conv(conv):
-        return ops.get().conv1x1(x, conv.weight, conv.bias)
+        return ops.get().conv1x1(x, conv.weight, conv.bias, mfma=config.mfma)
     return conv(x)
 
 
@@ -404,7 +411,7 @@ class LookupRef:
         if c.corr == "on_demand" and c.conv1x1 == "hip" and x.is_cuda and _is_plain1x1(conv) and _frozen_conv(conv):
             # no fused on-demand form: convc1 on the materialised lookup through the package's own 1x1 product (no
             # library kernel), then bias + ReLU in one pass
-            return ops.get().bias_relu(ops.get().conv1x1(x, conv.weight, None), conv.bias)
+            return ops.get().bias_relu(ops.get().conv1x1(x, conv.weight, None, mfma=c.mfma), conv.bias)
         return _conv_relu(conv, x)
 
 
@@ -465,7 +472,7 @@ def mask_logits(head, net, cache):
             cache["key"], cache["w"], cache["b"] = key, (.25 * c2.weight).contiguous(), (.25 * c2.bias).contiguous()
     y = _conv_relu(c0, net)
     if cfg(head).conv1x1 == "hip" and y.is_cuda and _is_plain1x1(c2):
-        return ops.get().conv1x1(y, cache["w"], cache["b"])
+        return ops.get().conv1x1(y, cache["w"], cache["b"], mfma=cfg(head).mfma)
     return c2._conv_forward(y, cache["w"], cache["b"])
 
 
@@ -551,7 +558,8 @@ class RAFT(nn.Module):
                                                   radius=self.args["corr_radius"])
         else:
             corr_fn = ops.get().CorrBlock(_f32(fmap1), _f32(fmap2), num_levels=self.args["corr_levels"],
-                                          radius=self.args["corr_radius"], bwd_windows=cfg(self).pyramid_bwd_windows)
+                                          radius=self.args["corr_radius"], bwd_windows=cfg(self).pyramid_bwd_windows,
+                                          **mfma_kw(cfg(self)))
         if side is not None:
             main.wait_stream(side)
         else:

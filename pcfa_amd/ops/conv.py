@@ -38,8 +38,11 @@ class _Conv1x1(torch.autograd.Function):
     (attack_PCFA.PairsInFlight) and does not depend on which solution the library picks for a shape."""
 
     @staticmethod
-    def forward(ctx, x, w, b):
+    def forward(ctx, x, w, b, mfma="f32"):
         _dev(x, w)
+        if mfma not in ("f32", "bf16x3"):
+            raise ValueError("conv1x1: mfma must be 'f32' or 'bf16x3', got %r" % (mfma,))
+        entry = "pcfa_gemm_f32" if mfma == "f32" else "pcfa_gemm_bf16x3"   # Config.mfma: same contract, split-bf16 products
         if w.dim() != 4 or tuple(w.shape[2:]) != (1, 1) or x.dim() != 4 or x.shape[1] != w.shape[1]:
             raise ValueError("conv1x1: weight %s does not fit input %s" % (tuple(w.shape), tuple(x.shape)))
         if x.dtype != torch.float32 or w.dtype != torch.float32:
@@ -50,12 +53,13 @@ class _Conv1x1(torch.autograd.Function):
         w2 = w.reshape(N, K).contiguous()
         out = torch.empty((B, N, H, W), device=x.device, dtype=torch.float32)
         # C[b][n][p] = sum_k W[n][k] X[b][k][p]: A = W stored [M][K] (shared by the batch: stride 0), B = X[b] stored [K][N]
-        _call("pcfa_gemm_f32", _ptr(w2), _ptr(x), _ptr(out), N, hw, K, K, hw, hw, 0, 1, B, 0, K * hw, N * hw, 1.0, 1,
+        _call(entry, _ptr(w2), _ptr(x), _ptr(out), N, hw, K, K, hw, hw, 0, 1, B, 0, K * hw, N * hw, 1.0, 1,
               _ptr(None), ctypes.c_size_t(0))
         if b is not None:
             out.add_(b.view(1, N, 1, 1))
         ctx.save_for_backward(w2)
         ctx.dims = (B, K, N, H, W)
+        ctx.entry = entry
         return out
 
     @staticmethod
@@ -69,14 +73,15 @@ class _Conv1x1(torch.autograd.Function):
         g = g.contiguous()
         gx = torch.empty((B, K, H, W), device=g.device, dtype=torch.float32)
         # dX[b][k][p] = sum_n W[n][k] G[b][n][p]: A = W stored [K' = N][M' = K], B = G[b] stored [K' = N][N' = hw]
-        _call("pcfa_gemm_f32", _ptr(w2), _ptr(g), _ptr(gx), K, hw, N, K, hw, hw, 1, 1, B, 0, N * hw, K * hw, 1.0, 1,
+        _call(ctx.entry, _ptr(w2), _ptr(g), _ptr(gx), K, hw, N, K, hw, hw, 1, 1, B, 0, N * hw, K * hw, 1.0, 1,
               _ptr(None), ctypes.c_size_t(0))
-        return gx, None, None
+        return gx, None, None, None
 
 
-def conv1x1(x, weight, bias=None):
-    """conv2d(x, weight[N,K,1,1], bias), stride 1, frozen weights, without a library kernel (see _Conv1x1)."""
-    return _Conv1x1.apply(x, weight, bias)
+def conv1x1(x, weight, bias=None, mfma="f32"):
+    """conv2d(x, weight[N,K,1,1], bias), stride 1, frozen weights, without a library kernel (see _Conv1x1); mfma
+    (Config.mfma): "f32" | "bf16x3"."""
+    return _Conv1x1.apply(x, weight, bias, mfma)
 
 
 def conv_fewin(x, weight, bias=None, relu=False):

@@ -16,7 +16,7 @@ from .core import _call, _dev, _note_work, _pair, _ptr, _ptr_off, _stream, cache
 # --------------------------------------------------------------------------- #
 class _CorrState:
     """Device buffers shared by the build node and its lookup nodes."""
-    __slots__ = ("B", "D", "H", "W", "L", "r", "slab", "pyr", "f2ext", "dpyr", "token_grad", "coords_bwd", "bwd_windows")
+    __slots__ = ("B", "D", "H", "W", "L", "r", "slab", "pyr", "f2ext", "dpyr", "token_grad", "coords_bwd", "bwd_windows", "mfma")
 
 
 class _CorrBuild(torch.autograd.Function):
@@ -37,8 +37,8 @@ class _CorrBuild(torch.autograd.Function):
         state.f2ext = torch.empty((B, D, slab), device=f1.device, dtype=torch.float32)
         state.pyr = torch.empty((B * H * W, slab), device=f1.device, dtype=torch.float32)
         _call("pcfa_corr_f2ext_fwd", _ptr(f2), _ptr(state.f2ext), B, D, H, W, state.L)
-        _call("pcfa_corr_pyramid_fwd", _ptr(f1), _ptr(state.f2ext), _ptr(state.pyr), B, D, H, W,
-                                             state.L)
+        _call("pcfa_corr_pyramid_fwd" if state.mfma == "f32" else "pcfa_corr_pyramid_fwd_bf16x3", _ptr(f1),
+              _ptr(state.f2ext), _ptr(state.pyr), B, D, H, W, state.L)
         ctx.state = state
         ctx.save_for_backward(f1)
         return torch.zeros(1, device=f1.device, dtype=torch.float32)
@@ -179,10 +179,13 @@ class _CorrLookupConv(torch.autograd.Function):
 class CorrBlock:
     """Drop-in for models/raft/corr.py:12-50 -- same constructor and __call__."""
 
-    def __init__(self, fmap1, fmap2, num_levels=4, radius=4, bwd_windows=True):
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4, bwd_windows=True, mfma="f32"):
         """bwd_windows (Config.pyramid_bwd_windows): the backward products skip what no lookup window touched; False =
-        the dense products (A/B, parity tests)."""
+        the dense products (A/B, parity tests).  mfma (Config.mfma): "f32" | "bf16x3", the arithmetic of the pyramid's
+        FORWARD product (pcfa_corr_pyramid_fwd_bf16x3); the backward products stay on the fp32 matrix cores."""
         _dev(fmap1, fmap2)
+        if mfma not in ("f32", "bf16x3"):
+            raise ValueError("CorrBlock: mfma must be 'f32' or 'bf16x3', got %r" % (mfma,))
         if fmap1.shape != fmap2.shape or fmap1.dim() != 4:
             raise ValueError("CorrBlock expects two [B,D,H,W] feature maps of equal shape")
         lib = _hip.load()
@@ -198,6 +201,7 @@ class CorrBlock:
         st.token_grad = None
         st.coords_bwd = None
         st.bwd_windows = bool(bwd_windows)
+        st.mfma = mfma
         self._state = st
         self._token = _CorrBuild.apply(fmap1, fmap2, st)
 

@@ -15,10 +15,23 @@ from .core import _call, _dev, _note_work, _pair, _ptr, _ptr_off, _stream
 # --------------------------------------------------------------------------- #
 # GMA attention (models/gma/gma.py:34-77,79-115)
 # --------------------------------------------------------------------------- #
-def gemm_f32(a, b, a_kmajor, b_kmajor, alpha=1.0, splits=1, out=None):
-    """C[..., m, n] = alpha * sum_k A(m, k) B(k, n) on the fp32 matrix cores (pcfa_gemm_f32).  `a` is [.., M, K]
-    (a_kmajor = 0) or [.., K, M] (1); `b` is [.., N, K] (b_kmajor = 0) or [.., K, N] (1); leading dims = batch."""
+MFMA_MODES = ("f32", "bf16x3")
+
+
+def gemm_entry(mfma):
+    """The GEMM core's entry point for Config.mfma: "f32" -> pcfa_gemm_f32 (v_mfma_f32_32x32x2_f32), "bf16x3" ->
+    pcfa_gemm_bf16x3 (three bf16 pieces per fp32 operand, six v_mfma_f32_32x32x16_bf16 products; same contract)."""
+    if mfma not in MFMA_MODES:
+        raise ValueError("mfma must be 'f32' or 'bf16x3', got %r" % (mfma,))
+    return "pcfa_gemm_f32" if mfma == "f32" else "pcfa_gemm_bf16x3"
+
+
+def gemm_f32(a, b, a_kmajor, b_kmajor, alpha=1.0, splits=1, out=None, mfma="f32"):
+    """C[..., m, n] = alpha * sum_k A(m, k) B(k, n) on the matrix cores, fp32 in and out (pcfa_gemm_f32, or
+    pcfa_gemm_bf16x3 under mfma = "bf16x3").  `a` is [.., M, K] (a_kmajor = 0) or [.., K, M] (1); `b` is [.., N, K]
+    (b_kmajor = 0) or [.., K, N] (1); leading dims = batch."""
     _dev(a, b)
+    entry = gemm_entry(mfma)
     a, b = a.contiguous(), b.contiguous()
     M, K = (a.shape[-1], a.shape[-2]) if a_kmajor else (a.shape[-2], a.shape[-1])
     N = b.shape[-1] if b_kmajor else b.shape[-2]
@@ -32,19 +45,21 @@ def gemm_f32(a, b, a_kmajor, b_kmajor, alpha=1.0, splits=1, out=None):
     lib = _hip.load()
     ws, nbytes = None, 0
     if splits > 1:
-        nbytes = int(lib.pcfa_gemm_f32_workspace_bytes(M, N, batch, splits))
+        nbytes = int(getattr(lib, entry + "_workspace_bytes")(M, N, batch, splits))
         ws = torch.empty(nbytes // 4, device=a.device, dtype=torch.float32)
-    _call("pcfa_gemm_f32", _ptr(a), _ptr(b), _ptr(out), M, N, K, a.shape[-1], b.shape[-1], N, int(a_kmajor),
+    _call(entry, _ptr(a), _ptr(b), _ptr(out), M, N, K, a.shape[-1], b.shape[-1], N, int(a_kmajor),
           int(b_kmajor), batch, M * K, N * K, M * N, float(alpha), int(splits), _ptr(ws), ctypes.c_size_t(nbytes))
     return out
 
 
-def _attn_mm(a, b, a_kmajor, b_kmajor, alpha=1.0, splits=1, gemm="lib"):
+def _attn_mm(a, b, a_kmajor, b_kmajor, alpha=1.0, splits=1, gemm="lib", mfma="f32"):
     """A plain GEMM of the attention block.  gemm = "lib" (Config.gma_gemm's default): the library (rocBLAS through
     torch.matmul) -- these are plain dense products and it runs them at 107-126 TFLOP/s; "hip" routes them through
-    pcfa_gemm_f32 (80-105 TFLOP/s, tools/bench_gemm.py), which the parity test exercises either way."""
+    pcfa_gemm_f32 (80-105 TFLOP/s, tools/bench_gemm.py), which the parity test exercises either way.  mfma
+    (Config.mfma) picks the hand-written core's arithmetic and has no effect on the library product."""
     if gemm == "hip":
-        return gemm_f32(a, b, a_kmajor, b_kmajor, alpha=alpha, splits=splits)
+        return gemm_f32(a, b, a_kmajor, b_kmajor, alpha=alpha, splits=splits, mfma=mfma)
+    gemm_entry(mfma)   # validates
     at = a.transpose(-1, -2) if a_kmajor else a
     bt = b if b_kmajor else b.transpose(-1, -2)
     out = torch.matmul(at, bt)
@@ -58,11 +73,11 @@ class _AttentionSoftmax(torch.autograd.Function):
     rowsum(g * attn)) in one pass, dq = scale * dsim k, dk = scale * dsim^T q."""
 
     @staticmethod
-    def forward(ctx, q, k, scale, gemm="lib"):
+    def forward(ctx, q, k, scale, gemm="lib", mfma="f32"):
         _dev(q, k)
-        ctx.gemm = gemm
+        ctx.gemm, ctx.mfma = gemm, mfma
         q, k = q.contiguous(), k.contiguous()
-        sim = _attn_mm(q, k, 0, 0, alpha=scale, gemm=gemm)            # [.., N, N]
+        sim = _attn_mm(q, k, 0, 0, alpha=scale, gemm=gemm, mfma=mfma)            # [.., N, N]
         n = sim.shape[-1]
         _call("pcfa_softmax_rows_fwd", _ptr(sim), _ptr(sim), sim.numel() // n, n)
         ctx.scale = float(scale)
@@ -80,14 +95,16 @@ class _AttentionSoftmax(torch.autograd.Function):
         # g, one write); the price is a 198 MB temporary at 55x128.
         ds = torch.empty_like(g)
         _call("pcfa_softmax_rows_bwd", _ptr(attn), _ptr(g), _ptr(ds), attn.numel() // n, n)
-        dq = _attn_mm(ds, k, 0, 1, alpha=ctx.scale, splits=8, gemm=ctx.gemm) if ctx.needs_input_grad[0] else None  # dsim k
-        dk = _attn_mm(ds, q, 1, 1, alpha=ctx.scale, splits=8, gemm=ctx.gemm) if ctx.needs_input_grad[1] else None  # dsim^T q
-        return dq, dk, None, None
+        mm = dict(alpha=ctx.scale, splits=8, gemm=ctx.gemm, mfma=ctx.mfma)
+        dq = _attn_mm(ds, k, 0, 1, **mm) if ctx.needs_input_grad[0] else None  # dsim k
+        dk = _attn_mm(ds, q, 1, 1, **mm) if ctx.needs_input_grad[1] else None  # dsim^T q
+        return dq, dk, None, None, None
 
 
-def attention_softmax(q, k, scale, gemm="lib"):
-    """softmax(scale * q k^T, dim=-1) for q, k [.., N, d]; gemm: "lib" | "hip" (Config.gma_gemm)."""
-    return _AttentionSoftmax.apply(q, k, scale, gemm)
+def attention_softmax(q, k, scale, gemm="lib", mfma="f32"):
+    """softmax(scale * q k^T, dim=-1) for q, k [.., N, d]; gemm: "lib" | "hip" (Config.gma_gemm); mfma: "f32" |
+    "bf16x3" (Config.mfma; the arithmetic of the "hip" products)."""
+    return _AttentionSoftmax.apply(q, k, scale, gemm, mfma)
 
 
 class AttnGradShare:
@@ -96,10 +113,12 @@ class AttnGradShare:
     ONE product [g_1 | .. | g_n] [v_1 | .. | v_n]^T (K = n * 128) instead of n read-modify-write products over the
     198 MB matrix."""
 
-    def __init__(self, gemm="lib"):
+    def __init__(self, gemm="lib", mfma="f32"):
         self.pending = 0
         self.gs, self.vs = [], []
         self.gemm = gemm   # "lib" | "hip" (Config.gma_gemm): which GEMM the nodes sharing this object run
+        self.mfma = mfma   # "f32" | "bf16x3" (Config.mfma): the arithmetic of the "hip" products
+        gemm_entry(mfma)
 
 
 class _AttnTimesValue(torch.autograd.Function):
@@ -110,7 +129,7 @@ class _AttnTimesValue(torch.autograd.Function):
         ctx.save_for_backward(attn, v)
         ctx.shared = shared
         shared.pending += 1
-        return _attn_mm(attn, v, 0, 1, splits=8, gemm=shared.gemm)     # [.., N, d]
+        return _attn_mm(attn, v, 0, 1, splits=8, gemm=shared.gemm, mfma=shared.mfma)     # [.., N, d]
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -118,7 +137,7 @@ class _AttnTimesValue(torch.autograd.Function):
         attn, v = ctx.saved_tensors
         sh = ctx.shared
         g = g.contiguous()
-        dv = _attn_mm(attn, g, 1, 1, splits=8, gemm=sh.gemm) if ctx.needs_input_grad[1] else None     # attn^T g
+        dv = _attn_mm(attn, g, 1, 1, splits=8, gemm=sh.gemm, mfma=sh.mfma) if ctx.needs_input_grad[1] else None     # attn^T g
         d_attn = None
         if ctx.needs_input_grad[0]:
             if sh.pending <= 0:
@@ -130,7 +149,7 @@ class _AttnTimesValue(torch.autograd.Function):
             if sh.pending == 0:
                 gcat, vcat = torch.cat(sh.gs, dim=-1), torch.cat(sh.vs, dim=-1)
                 sh.gs, sh.vs = [], []
-                d_attn = _attn_mm(gcat, vcat, 0, 0, gemm=sh.gemm)      # [.., N, N], K = n * d
+                d_attn = _attn_mm(gcat, vcat, 0, 0, gemm=sh.gemm, mfma=sh.mfma)      # [.., N, N], K = n * d
         return d_attn, dv, None
 
 

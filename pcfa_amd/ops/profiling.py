@@ -41,6 +41,7 @@ class DispatchTimer:
         "pcfa_corr_lookup_fwd": [("corr_lookup_fwd", 0)],
         "pcfa_corr_lookup_bwd": [("corr_lookup_bwd", 0)],
         "pcfa_corr_pyramid_fwd": [("corr_pyramid_gemm_fwd", 0)],
+        "pcfa_corr_pyramid_fwd_bf16x3": [("corr_pyramid_gemm_fwd", 0)],   # Config.mfma = "bf16x3": the same product
         "pcfa_corr_pyramid_bwd": [("corr_pyramid_gemm_dfmap1", 0), ("corr_pyramid_gemm_df2ext", 2)],
         "pcfa_corr_pyramid_bwd_windows": [("corr_pyramid_gemm_dfmap1", 2), ("corr_pyramid_gemm_df2ext", 4)],
         "pcfa_corr_f2ext_fwd": [("corr_f2ext_fwd", 0)],
