@@ -427,12 +427,7 @@ def sepconv5_problem(B, Cin, Cout, H, W, vertical, backward, wino, groups):
                                    partials=wg.chunk_partials(Cin, [("interleave", groups)]))
     else:
         P = F.conv2d(x.double().abs(), w4.abs(), padding=pad)
-        xp = F.pad(x, (0, 0, 2, 2) if vertical else (2, 2, 0, 0))
-        emu = torch.zeros(B, Cout, H, W)
-        for c in range(Cin):
-            for t in range(5):
-                xs = xp[:, c, t:t + H, :] if vertical else xp[:, c, :, t:t + W]
-                emu = emu + weff[:, c, t].view(1, -1, 1, 1) * xs.unsqueeze(1)
+        emu = wg.direct_sepconv5_fp32(x, weff, vertical)
     return x, wt, want, P, emu
 
 

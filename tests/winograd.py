@@ -20,6 +20,14 @@ n counts the roundings on the longest path through the kernel's order of operati
   F25: weight transform 1, input transform 2, Cin terms, KS - 1 <= 3 group partials, output transform 3, accumulate
        into the output 1:                                                                 n = Cin + 10
   direct sepconv5 (implicit GEMM): 5 Cin products, the split2 partial addition 1, accumulate 1:   n = 5 Cin + 2
+  The fused SepConvGRU epilogues of both sepconv5 kernels (tests/gru_epilogue.py) add to the convolution's n:
+    mode 1 gates_fwd : + 1 (add_zr); z, r: the device sigmoid (c_sigmoid u |z|);  rh = r h: 1
+    mode 2 update_fwd: + 1 (add_q);  q: the device tanhf (c_tanh u |q|);  hnew = (1 - z) h + z q: 4
+    mode 3 gates_bwd : dzr[:, :C] = dz (1 - z) z: 3 (no convolution);  dzr[:, C:] = ((drh h)(1 - r)) r: 4;
+                       dh = drh r + dh_in: 2 (1 without dh_in);  d_rest: the plain accumulate of n
+    mode 4 update_bwd: + 1 (g = dh_acc + ddh);  dz = g q - g h: 3;  dqc = (g z)(1 - q q): 4;  dh = g (1 - z): 2;
+                       d_rest: the plain accumulate of n
+  each product and each addition of the expression counted once, which covers a contraction to fma either way.
 c = 2 covers an MFMA that rounds each product and each addition separately; tiny = n 2^-126 covers flushed
 subnormals.  Tests add 2 spare roundings to each count.  The activation is applied to the float64 pre-activation:
 ReLU and LeakyReLU are 1-Lipschitz, so the bound of the pre-activation holds for the activated value as well; a mask
@@ -115,6 +123,19 @@ def winograd_sepconv5(x, w, vertical, absval=False, dtype=torch.float64, partial
     M = _accumulate(V, U, "bkhti,nki->bnhti", partials, dtype)
     Y = (M @ AT.T).reshape(B, -1, H, 2 * tw)[..., :W]
     return Y.transpose(2, 3) if vertical else Y
+
+
+def direct_sepconv5_fp32(x, w, vertical):
+    """The direct implicit GEMM of csrc/sepconv5.hip emulated in fp32: the 5 Cin products added term by term, zero
+    outside the image."""
+    B, Cin, H, W = x.shape
+    xp = torch.nn.functional.pad(x, (0, 0, 2, 2) if vertical else (2, 2, 0, 0))
+    emu = torch.zeros(B, w.shape[0], H, W)
+    for c in range(Cin):
+        for t in range(5):
+            xs = xp[:, c, t:t + H, :] if vertical else xp[:, c, :, t:t + W]
+            emu += w[:, c, t].view(1, -1, 1, 1) * xs.unsqueeze(1)
+    return emu
 
 
 def chunk_partials(K, splits):
