@@ -407,8 +407,8 @@ __global__ void resample2d_fwd_kernel(const float* __restrict__ in1, const float
       dst[(size_t)c * plane] = val;
     }
   } else {
-    const int xN = max(min((int)floorf(xf + 0.5f), W - 1), 0);
-    const int yN = max(min((int)floorf(yf + 0.5f), H - 1), 0);
+    const int xN = max(min(tap_index(floorf(xf + 0.5f)), W - 1), 0);
+    const int yN = max(min(tap_index(floorf(yf + 0.5f)), H - 1), 0);
     for (int c = 0; c < C; ++c) dst[(size_t)c * plane] = src[(size_t)c * iplane + (size_t)yN * iW + xN];
   }
 }

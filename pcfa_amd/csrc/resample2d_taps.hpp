@@ -3,6 +3,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+// floor -> tap index for ANY float: (int) of a value outside int's range, or of NaN, is undefined, so the floor is clamped
+// to +-1e8 before the conversion (fmaxf / fminf return the other operand for NaN: NaN -> -1e8), as make_origin of the
+// correlation lookups does.  Every index, window cell and difference formed from the result stays far inside int; for a
+// floor within +-1e8 -- any image -- the value is the plain conversion's.
+__device__ __forceinline__ int tap_index(float f) { return (int)fminf(fmaxf(f, -1.0e8f), 1.0e8f); }
+
 struct RsTaps {
   int xL, xR, yT, yB;
   float alpha, beta;
@@ -13,10 +19,10 @@ __device__ __forceinline__ RsTaps rs_taps(float xf, float yf, int h, int w) {
   const float fx = floorf(xf), fy = floorf(yf);
   t.alpha = xf - fx;
   t.beta = yf - fy;
-  t.xL = max(min((int)fx, w - 1), 0);
-  t.xR = max(min((int)(fx + 1.f), w - 1), 0);
-  t.yT = max(min((int)fy, h - 1), 0);
-  t.yB = max(min((int)(fy + 1.f), h - 1), 0);
+  t.xL = max(min(tap_index(fx), w - 1), 0);
+  t.xR = max(min(tap_index(fx + 1.f), w - 1), 0);
+  t.yT = max(min(tap_index(fy), h - 1), 0);
+  t.yB = max(min(tap_index(fy + 1.f), h - 1), 0);
   return t;
 }
 
@@ -33,9 +39,10 @@ __device__ __forceinline__ void resample2d_bwd_pixel(const float* __restrict__ i
   const float dx = flow[((size_t)b * 2) * plane + (size_t)y * W + x];
   const float dy = flow[((size_t)b * 2 + 1) * plane + (size_t)y * W + x];
   const float xf = (float)x + dx, yf = (float)y + dy;
-  // grad_in1: neighbours clamped against the INPUT size, weights from truncation (xf - int(xf), :103-111)
+  // grad_in1: neighbours clamped against the INPUT size, weights from truncation (xf - int(xf), :103-111; truncf is
+  // (float)(int) wherever that is defined)
   const RsTaps t1 = rs_taps(xf, yf, iH, iW);
-  const float a1 = xf - (float)(int)xf, b1 = yf - (float)(int)yf;
+  const float a1 = xf - truncf(xf), b1 = yf - truncf(yf);
   // grad_flow: neighbours clamped against the flow size, gamma = 1 - frac (:159-170)
   const RsTaps t2 = rs_taps(xf, yf, H, W);
   const float gam_x = 1.f - t2.alpha, gam_y = 1.f - t2.beta;

@@ -63,8 +63,8 @@ __device__ __forceinline__ float tap_fma(float acc, float v, float w, float g, b
 __device__ __forceinline__ WarpTaps warp_taps(float ix, float iy, int H, int W) {
   WarpTaps t;
   const float fx = floorf(ix), fy = floorf(iy);
-  t.x0 = (int)fx;
-  t.y0 = (int)fy;
+  t.x0 = tap_index(fx);   // (clamped to +-1e8: x0 + 1, x0 - window origin and the tile centre's x0 - 15 cannot overflow)
+  t.y0 = tap_index(fy);
   t.wx1 = ix - fx;
   t.wy1 = iy - fy;
   t.vx0 = t.x0 >= 0 && t.x0 < W;

@@ -20,6 +20,7 @@ import torch.nn.functional as F
 from pcfa_amd import config as pcfa_config
 from pcfa_amd import hip_ops
 from tests import closure_util
+from tests import warp as warp_ref
 from tests.fenced import NAN_BITS, SENTINEL, TINY, U, Fenced, gamma
 from tests.util import load_golden, rel_l2, t
 
@@ -204,33 +205,12 @@ def test_conv_s2_leaky_op_autograd(k, H, W):
 
 
 # --------------------------------------------------------------------------- Resample2d, nearest x4
-def resample2d_ref64(x, flow, gout):
-    """Resample2d's backward restated in float64 (resample2d_kernel.cu:75-201, as ops.flownet2.resample2d_det documents):
-    grad_in1 with truncation weights and neighbours clamped to the image, grad_flow by the reference's gather."""
-    B, C, H, W = x.shape
-    yy, xx = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
-    xf = xx + flow[:, 0]
-    yf = yy + flow[:, 1]
-    fx, fy = torch.floor(xf), torch.floor(yf)
-    xL = fx.long().clamp(0, W - 1)
-    xR = (fx + 1).long().clamp(0, W - 1)
-    yT = fy.long().clamp(0, H - 1)
-    yB = (fy + 1).long().clamp(0, H - 1)
-    a1 = (xf - xf.long().float()).double()
-    b1 = (yf - yf.long().float()).double()
-    g64 = gout.double()
-    gx = torch.zeros(B, C, H * W, dtype=torch.float64)
-    for yi, xi, wgt in ((yT, xL, (1 - a1) * (1 - b1)), (yT, xR, a1 * (1 - b1)), (yB, xL, (1 - a1) * b1),
-                        (yB, xR, a1 * b1)):
-        idx = (yi * W + xi).view(B, 1, H * W).expand(B, C, H * W)
-        gx.scatter_add_(2, idx, (wgt.unsqueeze(1) * g64).view(B, C, H * W))
-    return gx.view(B, C, H, W)
-
-
 @pytest.mark.parametrize("B,H,W,amp", [(1, 128, 192, 3.0), (2, 436, 1024, 20.0), (1, 13, 27, 40.0)])
 def test_resample2d_det_against_float64(B, H, W, amp):
-    """grad_in1 within the fixed-point quantum of a float64 restatement, grad_flow and the forward equal to the atomic
-    library path's (same arithmetic), identical bits on repeated calls and across graph replays."""
+    """grad_in1 and grad_flow per element against the float64 restatement of tests/warp.py (grad_in1: the rounding of an
+    addend's products and of the finish, plus half a fixed-point unit per addend that lands on the texel; grad_flow: the
+    eight-term chains), grad_flow and the forward equal to the atomic library path's (same arithmetic), identical bits on
+    repeated calls and across graph replays."""
     C = 3
     g = torch.Generator().manual_seed(H + W + B)
     x = torch.randn(B, C, H, W, generator=g)
@@ -248,12 +228,10 @@ def test_resample2d_det_against_float64(B, H, W, amp):
     g1a, g2a = torch.autograd.grad(out_a, (xa, fa), gd)
     assert torch.equal(res[0][0], out_a) and torch.equal(res[0][2], g2a)
     assert rel_l2(res[0][1], g1a) < 1e-6
-    ref = resample2d_ref64(x, flow, gout)
-    # each addend carries <= half a unit of 2^(floor(log2 max|g|) - 40), at most 4 H W addends land on one pixel; plus the
-    # fp32 rounding of the finish and of the addends' weight products
-    unit = 2.0 ** (math.floor(math.log2(float(gout.abs().max()))) - 40)
-    err = (res[0][1].cpu().double() - ref).abs()
-    assert bool((err <= 0.5 * unit * 4 * H * W + 4 * U * (ref.abs() + 4 * float(gout.abs().max()))).all())
+    # per texel: 2 gamma(5) sum |w g| + k unit / 2, k the texel's own addend count; grad_flow: 2 gamma(4 C + 4) P + u A
+    (ref1, bound1), (ref2, bound2) = warp_ref.resample2d_reference(x, flow, gout)
+    assert bool(((res[0][1].cpu().double() - ref1).abs() <= bound1).all())
+    assert bool(((res[0][2].cpu().double() - ref2).abs() <= bound2).all())
     for a, b in zip(res[0], res[1]):
         assert torch.equal(a.view(torch.int32), b.view(torch.int32))
     # graph replays: the same bits as the eager call

@@ -19,6 +19,7 @@ import torch.nn.functional as F
 from pcfa_amd import config as pcfa_config
 from pcfa_amd import hip_ops
 from tests import closure_util
+from tests import warp as warp_ref
 from tests.util import load_golden, rel_l2, t
 
 pytestmark = pytest.mark.gpu
@@ -142,8 +143,11 @@ def _spy_warp_ref(feat, flow):
 @pytest.mark.parametrize("B,C,H,W,amp", [(1, 3, 14, 32, 3.0), (2, 3, 56, 128, 40.0), (1, 3, 30, 47, 10.0),
                                           (1, 3, 448, 1024, 60.0)])
 def test_spynet_warp_against_grid_sample(B, C, H, W, amp):
-    """Forward within 4 ulp of max|x| of ATen's GPU grid_sample; both gradients against float64 CPU grid_sample + clamp
-    autograd (flows large enough to push the grid past +-1: the clamp mask is exercised); repeated calls identical."""
+    """Forward within 4 ulp of max|x| of ATen's GPU grid_sample; the forward and both gradients per element against
+    float64 computed from the mirrored fp32 sample positions (tests/warp.py: no pixel can fall into another cell, every
+    pixel and texel is decided); both gradients against float64 CPU grid_sample + clamp autograd (flows large enough to
+    push the grid past +-1: the clamp mask is exercised) -- a coarse statement, float64 positions fall into other cells;
+    repeated calls identical."""
     g = torch.Generator().manual_seed(H * W + B)
     x = torch.randn(B, C, H, W, generator=g)
     flo = torch.randn(B, 2, H, W, generator=g) * amp
@@ -165,6 +169,10 @@ def test_spynet_warp_against_grid_sample(B, C, H, W, amp):
     for _ in range(2):
         gx, gf = torch.autograd.grad(hip_ops.spynet_warp(xr, fr), (xr, fr), gout.to(DEV))
         res.append((gx.clone(), gf.clone()))
+    # per element, from the op's own linspace vectors: 2 gamma(7) P; 2 gamma(5) sum |w g| + k unit / 2; 2 gamma(n + 2) P
+    hor, ver = torch.linspace(-1.0, 1.0, W, device=DEV).cpu(), torch.linspace(-1.0, 1.0, H, device=DEV).cpu()
+    for got, (want, bound) in zip((out, res[0][0], res[0][1]), warp_ref.spynet_reference(x, flo, hor, ver, gout)):
+        assert bool(((got.cpu().double() - want).abs() <= bound).all())
     # the fp32 sample position carries ~u max(H, W) pixels of rounding (ATen's GPU kernel too): 3e-5 of d x at W = 1024
     tol = max(1e-5, 2 * U * max(H, W))
     assert rel_l2(res[0][0].cpu().double(), gx64) < tol
