@@ -173,6 +173,24 @@ PCFA_API int pcfa_corr_ondemand_bwd(void* workspace, const float* coords, const 
 PCFA_API int pcfa_corr_ondemand_finish(const void* workspace, float* dfmap1, float* dfmap2, int B, int D, int H, int W,
                               int num_levels, void* stream);
 
+/* The tiled execution of the same lookup (Config.ondemand_lookup = "tiled"); arguments and results as fwd / bwd above, to
+ * fp32 rounding.  Queries are grouped into tiles of tile_w x tile_h (raster order, edge tiles partial).  Per lookup one
+ * launch classifies every (tile, level) pair on the device: with x0 / y0 the window origins of the tile's live queries,
+ * bw = max x0 - min x0 + 2r+2, bh likewise; the pair takes the matrix route iff every live coordinate is finite with
+ * |floor(c / 2^l)| < 1e8 and bw * bh <= max_positions, else the per-query route (the kernels of fwd / bwd, which skip
+ * the other pairs).  Matrix route: the window dot products and both backward products of the tile run on the fp32
+ * matrix cores against the bw x bh box of pooled fmap2 rows; the fmap2 side is scattered per box element instead of
+ * per query and window position, through the same fixed-point accumulator.  No host read-back: graph-capturable.
+ * tile_geometry: host only.  tile_routes: counts[num_levels][2] (device ints) = pairs per level on the matrix /
+ * per-query route in the classification of the last tiled fwd or bwd on this workspace. */
+PCFA_API int pcfa_corr_ondemand_fwd_tiled(const void* workspace, const float* coords, float* out, int B, int D, int H,
+                                 int W, int num_levels, int radius, void* stream);
+PCFA_API int pcfa_corr_ondemand_bwd_tiled(void* workspace, const float* coords, const float* grad_out, int accumulate,
+                                 int B, int D, int H, int W, int num_levels, int radius, void* stream);
+PCFA_API int pcfa_corr_ondemand_tile_geometry(int* tile_w, int* tile_h, int* max_positions);
+PCFA_API int pcfa_corr_ondemand_tile_routes(const void* workspace, int B, int D, int H, int W, int num_levels,
+                                   int* counts, void* stream);
+
 /* GMA attention products and softmax (models/gma/gma.py:34-77 Attention, :79-115 Aggregate).
  * pcfa_gemm_f32: C[b][m][n] = alpha * sum_k A(m,k) B(k,n) on the fp32 matrix cores (the pyramid's GEMM core, exact
  * fp32 products).  a_kmajor 0: A stored [M][K] (lda = row stride), 1: stored [K][M]; b_kmajor 0: B stored [N][K],

@@ -49,6 +49,10 @@ SIGNATURES = {
     "pcfa_corr_ondemand_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "pcfa_corr_ondemand_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "pcfa_corr_ondemand_finish": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "pcfa_corr_ondemand_fwd_tiled": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "pcfa_corr_ondemand_bwd_tiled": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "pcfa_corr_ondemand_tile_geometry": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "pcfa_corr_ondemand_tile_routes": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "pcfa_gemm_f32_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "pcfa_gemm_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_longlong, c_longlong, c_longlong, c_int, c_int, c_int,
                               c_longlong, c_longlong, c_longlong, c_float, c_int, _P, c_size_t, _P]),

@@ -34,6 +34,9 @@ class Config:
                                          # a RAFT closure then holds no library kernel at all)
     corr: str = "all_pairs"              # correlation: "all_pairs" (CorrBlock: O(Q^2) pyramid, fused lookup -> convc1) |
                                          # "on_demand" (OnDemandCorrBlock: window dot products per lookup, O(Q*D) memory)
+    ondemand_lookup: str = "per_query"   # execution of corr="on_demand"'s lookups: "per_query" (one wave per query) | "tiled" (8x8
+                                         # query tiles whose windows share a small box run on the fp32 matrix cores, one
+                                         # fixed-point scatter per box element; wide tiles keep the per-query kernels)
     mfma: str = "f32"                    # arithmetic of the hand-written GEMM core: "f32" (v_mfma_f32_32x32x2_f32) | "bf16x3" (each
                                          # fp32 operand split into three bf16 pieces, six v_mfma_f32_32x32x16_bf16 products: fp32
                                          # accuracy at 16/6 of the fp32 matrix roof).  Takes effect where that core runs: the
@@ -69,6 +72,7 @@ class Config:
                    gma_attention=os.environ.get("PCFA_GMA_ATTENTION", "materialised"),
                    conv1x1=os.environ.get("PCFA_CONV1X1", "lib"),
                    corr=os.environ.get("PCFA_CORR", "all_pairs"),
+                   ondemand_lookup=os.environ.get("PCFA_ONDEMAND_LOOKUP", "per_query"),
                    mfma=os.environ.get("PCFA_MFMA", "f32"),
                    spynet_ops=os.environ.get("PCFA_SPYNET_OPS", "lib"),
                    flownet2_ops=os.environ.get("PCFA_FLOWNET2_OPS", "lib"),
@@ -83,6 +87,8 @@ class Config:
             raise ValueError("Config.conv1x1 must be 'lib' or 'hip', got %r" % (self.conv1x1,))
         if self.corr not in ("all_pairs", "on_demand"):
             raise ValueError("Config.corr must be 'all_pairs' or 'on_demand', got %r" % (self.corr,))
+        if self.ondemand_lookup not in ("per_query", "tiled"):
+            raise ValueError("Config.ondemand_lookup must be 'per_query' or 'tiled', got %r" % (self.ondemand_lookup,))
         if self.mfma not in ("f32", "bf16x3"):
             raise ValueError("Config.mfma must be 'f32' or 'bf16x3', got %r" % (self.mfma,))
         if self.spynet_ops not in ("lib", "hip"):

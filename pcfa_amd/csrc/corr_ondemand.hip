@@ -33,6 +33,31 @@
 // since |dC| <= max|grad_out| / sqrt(D) (the bilinear weights a position receives sum to <= 1) and at most Q queries of one
 // image add into one position: |sum| < 2^61.  Every addend keeps >= 61 - log2(Q) bits below the largest (>= 41 at 8K).
 // Either maximum can flag the lookup; dfmap1 then carries the NaN through its fp32 sums.
+//
+// Tiled execution (pcfa_corr_ondemand_fwd_tiled / _bwd_tiled, Config.ondemand_lookup = "tiled"; corr_ondemand_tiled.hpp).
+// Neighbouring queries look at neighbouring windows: the union of the windows of an 8x8 tile of queries at one level is a
+// box of P = bw * bh positions, small whenever the flow is locally smooth.
+//   classify : one launch per lookup, one wave per tile, on the device (no read-back: capturable).  Entry (tile, level) of
+//              the table `tab` (workspace, after `shift`; 16 B each) holds the box, or bw = 0 for the per-query route:
+//              a live coordinate that is not finite or meets the +-1e8 guard, or P > OD_MAXP (64-bit product).  Out-of-map
+//              box positions count towards P.
+//   forward  : workgroup = tile x level.  S[64 x P] = F1 F2box^T on v_mfma_f32_32x32x2_f32; out-of-map positions and dead
+//              query rows of an edge tile read the zero row.  Only each query's own (2r+2)^2 window of S is kept (26 KB of
+//              LDS whatever P), scaled by 1/sqrt(D); the blend is od_fwd_kernel's expression.  Dead rows are never stored.
+//   backward : workgroup = tile, looping over the levels on the matrix route.  Per chunk of 64 box positions dC[64 x 64] is
+//              built in LDS from the tap gradients (a query fills its own window, out-of-map positions and the rest are 0),
+//              dfmap1 += dC F2box (the tile owns its dfmap1 rows: one plain store at the end, honouring accumulate), and
+//              dF2box = dC^T F1 goes element by element through fix_quantize / fix_add into acc: P * D atomics per pair
+//              instead of 64 (2r+2)^2 D, exact zeros skipped, never an out-of-map position.
+//   The per-query kernels run after the tile kernels with `tab` as their predicate and serve the other pairs; in the
+//   backward they add to the dfmap1 rows the tile kernel wrote.  The launch order is fixed, no float atomics: two calls,
+//   two processes and two pairs in flight give the same bits.  All of it stays fp32 (Config.mfma has no effect here).
+//   OD_MAXP = 512: with only the windows kept, LDS does not bound P (26 KB forward, 39 KB backward: several workgroups
+//   per CU fit the 160 KB); what P bounds is the matrix work per pair, P / (2r+2)^2 times the products the windows need.
+//   512 keeps that factor at 5 and every box of a locally smooth flow (|d flow| < 1 per texel: 18 x 18 .. 21 x 21).
+//   od_shift_kernel's budget holds: a tile partial is an fp32 sum of n <= 64 terms, each |dC f1| <= M / 2, so its
+//   magnitude is at most n (1 + 64 u) M / 2; a position receives partials whose term counts sum to at most Q, hence
+//   |sum| <= Q (1 + 2^-18) (M / 2) 2^shift + 0.5 per partial < 2^61 with the factor 2 the unit leaves (M < 2^(ilogb M + 1)).
 #include "common.hpp"
 #include "fixed_point.hpp"
 
@@ -41,13 +66,15 @@ namespace {
 constexpr int OD_NBLK = 256;            // block maxima per |x| reduction
 constexpr int OD_QT = 16;               // queries per forward workgroup
 constexpr int OD_KMAX = 8;              // channels per lane in the backward: D <= 512
+constexpr int OD_TW = 8, OD_TH = 8;     // tiled execution: queries per tile (raster order inside the tile)
+constexpr int OD_MAXP = 512;            // box positions up to which a (tile, level) pair takes the matrix route
 
 struct OdLayout {
   int B, D, H, W, L, Q;
   int h[PCFA_MAX_LEVELS], w[PCFA_MAX_LEVELS];
   long long prow[PCFA_MAX_LEVELS];      // first row of level l (a row = D floats; [b][y][x] inside a level)
   long long rows;                       // B * sum_l h_l w_l; pyr row `rows` is the zero row
-  size_t o_f1t, o_pyr, o_acc, o_df2, o_df1, o_f1max, o_gmax, o_shift, bytes;
+  size_t o_f1t, o_pyr, o_acc, o_df2, o_df1, o_f1max, o_gmax, o_shift, o_tab, bytes;
 };
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -79,6 +106,7 @@ bool make_od_layout(OdLayout& Lo, int B, int D, int H, int W, int L) {
   Lo.o_f1max = o; o = align256(o + OD_NBLK * 4);
   Lo.o_gmax = o;  o = align256(o + OD_NBLK * 4);
   Lo.o_shift = o; o = align256(o + 4);
+  Lo.o_tab = o;   o = align256(o + (size_t)B * pcfa_cdiv(H, OD_TH) * pcfa_cdiv(W, OD_TW) * L * 16);   // OdTile entries
   Lo.bytes = o;
   return true;
 }
@@ -105,6 +133,10 @@ __device__ __forceinline__ Origin make_origin(float cx, float cy, int level, int
   o.y0 = (int)fminf(fmaxf(fly, -1.0e8f), 1.0e8f) - R;
   return o;
 }
+
+}  // namespace
+#include "corr_ondemand_tiled.hpp"   // OdTile, the classification and the tile kernels
+namespace {
 
 // ---- prepare -----------------------------------------------------------------------------------------------------------
 // [B][D][Q] -> [B][Q][D] through a 32 x 33 LDS tile; block (32, 8), grid (cdiv(Q,32), cdiv(D,32), B)
@@ -169,7 +201,8 @@ __global__ __launch_bounds__(256) void od_shift_kernel(const float* __restrict__
 template <int R>
 __global__ __launch_bounds__(256) void od_fwd_kernel(OdLayout Lo, const float* __restrict__ f1t,
                                                      const float* __restrict__ pyr, const float* __restrict__ coords,
-                                                     float* __restrict__ out, float inv_sqrt_d) {
+                                                     float* __restrict__ out, float inv_sqrt_d,
+                                                     const OdTile* __restrict__ tab) {
   constexpr int N1 = 2 * R + 1, WIN = 2 * R + 2, NPOS = WIN * WIN, NB = (NPOS + 63) / 64, NT = N1 * N1;
   static_assert(NT <= 128, "two taps per lane");
   __shared__ float s_dot[4][NB * 64];
@@ -179,15 +212,21 @@ __global__ __launch_bounds__(256) void od_fwd_kernel(OdLayout Lo, const float* _
   const int D = Lo.D, Q = Lo.Q, hl = Lo.h[l], wl = Lo.w[l];
   const float* zrow = pyr + (size_t)Lo.rows * D;
   const float* lvl = pyr + ((size_t)Lo.prow[l] + (size_t)b * hl * wl) * D;
+  // tab (the tiled execution): a query whose (tile, level) pair took the matrix route is skipped, here and in the store
+  if (tab != nullptr) {
+    const int q = min(q0 + (int)(threadIdx.x % OD_QT), Q - 1);
+    if (!__syncthreads_or(od_tile_of(tab, Lo, b, q, l).bw == 0)) return;
+  }
 
   for (int k = 0; k < OD_QT / 4; ++k) {
     const int qi = k * 4 + wv;                   // the four waves work on neighbouring queries at the same time
     const int q = min(q0 + qi, Q - 1);           // queries past the end compute a duplicate that is never stored
+    const bool mine = tab == nullptr || od_tile_of(tab, Lo, b, q, l).bw == 0;   // wave-uniform
     const float cx = coords[((size_t)b * 2) * Q + q], cy = coords[((size_t)b * 2 + 1) * Q + q];
     const Origin o = make_origin(cx, cy, l, R);
     const float* f1 = f1t + ((size_t)b * Q + q) * D;
 #pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
+    for (int nb = 0; nb < (mine ? NB : 0); ++nb) {
       float acc[64];
 #pragma unroll
       for (int i = 0; i < 64; ++i) acc[i] = 0.f;
@@ -237,7 +276,8 @@ __global__ __launch_bounds__(256) void od_fwd_kernel(OdLayout Lo, const float* _
   const size_t C = (size_t)Lo.L * NT;
   for (int i = threadIdx.x; i < NT * OD_QT; i += 256) {
     const int t = i / OD_QT, qi = i % OD_QT, q = q0 + qi;
-    if (q < Q) out[((size_t)b * C + (size_t)l * NT + t) * Q + q] = s_out[t][qi];
+    if (q < Q && (tab == nullptr || od_tile_of(tab, Lo, b, q, l).bw == 0))
+      out[((size_t)b * C + (size_t)l * NT + t) * Q + q] = s_out[t][qi];
   }
 }
 
@@ -247,7 +287,7 @@ __global__ __launch_bounds__(256) void od_bwd_kernel(OdLayout Lo, const float* _
                                                      const float* __restrict__ pyr, const float* __restrict__ coords,
                                                      const float* __restrict__ grad, float* __restrict__ df1,
                                                      long long* __restrict__ acc, const int* __restrict__ shiftp,
-                                                     int accumulate, float inv_sqrt_d) {
+                                                     int accumulate, float inv_sqrt_d, const OdTile* __restrict__ tab) {
   constexpr int N1 = 2 * R + 1, WIN = 2 * R + 2, NPOS = WIN * WIN, NT = N1 * N1;
   static_assert(NPOS <= 128, "two window positions per lane");
   __shared__ float s_g[4][128];
@@ -270,7 +310,10 @@ __global__ __launch_bounds__(256) void od_bwd_kernel(OdLayout Lo, const float* _
   }
   const float cx = coords[((size_t)b * 2) * Q + qc], cy = coords[((size_t)b * 2 + 1) * Q + qc];
   const size_t C = (size_t)Lo.L * NT;
+  bool any = tab == nullptr;   // tab (the tiled execution): levels on the matrix route are skipped (wave-uniform)
   for (int l = 0; l < Lo.L; ++l) {
+    const bool mine = tab == nullptr || od_tile_of(tab, Lo, b, qc, l).bw == 0;
+    any |= mine;
     const Origin o = make_origin(cx, cy, l, R);
     const int hl = Lo.h[l], wl = Lo.w[l];
 #pragma unroll
@@ -305,7 +348,7 @@ __global__ __launch_bounds__(256) void od_bwd_kernel(OdLayout Lo, const float* _
     float gl[OD_KMAX];   // this level's share: fp32 chains of <= (2r+2)^2 terms, not L (2r+2)^2
 #pragma unroll
     for (int k = 0; k < OD_KMAX; ++k) gl[k] = 0.f;
-    for (int p = 0; p < NPOS; ++p) {
+    for (int p = 0; p < (mine ? NPOS : 0); ++p) {
       const int X = o.x0 + p % WIN, Y = o.y0 + p / WIN;
       const float dc = s_dc[wv][p];
       if (X < 0 || X >= wl || Y < 0 || Y >= hl || dc == 0.f) continue;   // wave-uniform
@@ -324,7 +367,7 @@ __global__ __launch_bounds__(256) void od_bwd_kernel(OdLayout Lo, const float* _
     for (int k = 0; k < OD_KMAX; ++k) g1[k] += gl[k];
     __syncthreads();
   }
-  if (!live) return;
+  if (!live || !any) return;
   float* g = df1 + ((size_t)b * Q + q) * D;
 #pragma unroll
   for (int k = 0; k < OD_KMAX; ++k) {
@@ -396,19 +439,48 @@ int ceil_log2(long long v) {
 
 float inv_sqrt(int D) { return (float)(1.0 / sqrt((double)D)); }
 
+int od_tiles(const OdLayout& Lo) { return pcfa_cdiv(Lo.H, OD_TH) * pcfa_cdiv(Lo.W, OD_TW); }
+
+// tiled: classification, then the tile kernel, then the per-query kernel over the pairs the classification left to it
 template <int R>
-int launch_fwd(const OdLayout& Lo, const void* ws, const float* coords, float* out, hipStream_t s) {
+int launch_fwd(const OdLayout& Lo, const void* ws, const float* coords, float* out, bool tiled, hipStream_t s) {
+  const OdTile* tab = nullptr;
+  if (tiled) {
+    // the table is the one writable section behind a const workspace: a lookup owns it from its classification on
+    OdTile* wtab = at<OdTile>(const_cast<void*>(ws), Lo.o_tab);
+    tab = wtab;
+    pcfa_launch(od_classify_kernel<R>, dim3(od_tiles(Lo), Lo.B), dim3(64), 0, s, Lo, coords, wtab);
+    PCFA_LAUNCH_CHECK();
+    pcfa_launch(od_fwd_tile_kernel<R>, dim3(od_tiles(Lo), Lo.L, Lo.B), dim3(256), 0, s, Lo, at<float>(ws, Lo.o_f1t),
+                at<float>(ws, Lo.o_pyr), coords, tab, out, inv_sqrt(Lo.D));
+    PCFA_LAUNCH_CHECK();
+  }
   pcfa_launch(od_fwd_kernel<R>, dim3(pcfa_cdiv(Lo.Q, OD_QT), Lo.L, Lo.B), dim3(256), 0, s, Lo,
-              at<float>(ws, Lo.o_f1t), at<float>(ws, Lo.o_pyr), coords, out, inv_sqrt(Lo.D));
+              at<float>(ws, Lo.o_f1t), at<float>(ws, Lo.o_pyr), coords, out, inv_sqrt(Lo.D), tab);
   PCFA_LAUNCH_CHECK();
   return PCFA_OK;
 }
 
+// tiled: the tile kernel writes every dfmap1 row first (honouring accumulate), the per-query kernel then adds the levels
+// the classification left to it: a fixed launch order, so a fixed order of dfmap1's sums
 template <int R>
-int launch_bwd(const OdLayout& Lo, void* ws, const float* coords, const float* grad, int accumulate, hipStream_t s) {
+int launch_bwd(const OdLayout& Lo, void* ws, const float* coords, const float* grad, int accumulate, bool tiled,
+               hipStream_t s) {
+  const OdTile* tab = nullptr;
+  if (tiled) {
+    OdTile* wtab = at<OdTile>(ws, Lo.o_tab);
+    tab = wtab;
+    pcfa_launch(od_classify_kernel<R>, dim3(od_tiles(Lo), Lo.B), dim3(64), 0, s, Lo, coords, wtab);
+    PCFA_LAUNCH_CHECK();
+    pcfa_launch(od_bwd_tile_kernel<R>, dim3(od_tiles(Lo), Lo.B), dim3(256), 0, s, Lo, (const float*)at<float>(ws, Lo.o_f1t),
+                (const float*)at<float>(ws, Lo.o_pyr), coords, grad, tab, at<float>(ws, Lo.o_df1),
+                at<long long>(ws, Lo.o_acc), (const int*)at<int>(ws, Lo.o_shift), accumulate, inv_sqrt(Lo.D));
+    PCFA_LAUNCH_CHECK();
+    accumulate = 1;
+  }
   pcfa_launch(od_bwd_kernel<R>, dim3(pcfa_cdiv(Lo.Q, 4), Lo.B), dim3(256), 0, s, Lo, (const float*)at<float>(ws, Lo.o_f1t),
               (const float*)at<float>(ws, Lo.o_pyr), coords, grad, at<float>(ws, Lo.o_df1), at<long long>(ws, Lo.o_acc),
-              (const int*)at<int>(ws, Lo.o_shift), accumulate, inv_sqrt(Lo.D));
+              (const int*)at<int>(ws, Lo.o_shift), accumulate, inv_sqrt(Lo.D), tab);
   PCFA_LAUNCH_CHECK();
   return PCFA_OK;
 }
@@ -451,23 +523,24 @@ extern "C" int pcfa_corr_ondemand_prepare(const float* fmap1, const float* fmap2
   return PCFA_OK;
 }
 
-extern "C" int pcfa_corr_ondemand_fwd(const void* workspace, const float* coords, float* out, int B, int D, int H, int W,
-                                      int num_levels, int radius, void* stream) {
+namespace {
+int od_fwd(const void* workspace, const float* coords, float* out, int B, int D, int H, int W, int num_levels, int radius,
+           bool tiled, void* stream) {
   OdLayout Lo;
   if (!workspace || !coords || !out) return PCFA_ERR_INVALID_ARG;
   if (!make_od_layout(Lo, B, D, H, W, num_levels)) return PCFA_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   switch (radius) {
-    case 1: return launch_fwd<1>(Lo, workspace, coords, out, s);
-    case 2: return launch_fwd<2>(Lo, workspace, coords, out, s);
-    case 3: return launch_fwd<3>(Lo, workspace, coords, out, s);
-    case 4: return launch_fwd<4>(Lo, workspace, coords, out, s);
+    case 1: return launch_fwd<1>(Lo, workspace, coords, out, tiled, s);
+    case 2: return launch_fwd<2>(Lo, workspace, coords, out, tiled, s);
+    case 3: return launch_fwd<3>(Lo, workspace, coords, out, tiled, s);
+    case 4: return launch_fwd<4>(Lo, workspace, coords, out, tiled, s);
     default: return PCFA_ERR_UNSUPPORTED;
   }
 }
 
-extern "C" int pcfa_corr_ondemand_bwd(void* workspace, const float* coords, const float* grad_out, int accumulate, int B,
-                                      int D, int H, int W, int num_levels, int radius, void* stream) {
+int od_bwd(void* workspace, const float* coords, const float* grad_out, int accumulate, int B, int D, int H, int W,
+           int num_levels, int radius, bool tiled, void* stream) {
   OdLayout Lo;
   if (!workspace || !coords || !grad_out) return PCFA_ERR_INVALID_ARG;
   if (!make_od_layout(Lo, B, D, H, W, num_levels) || radius < 1 || radius > 4) return PCFA_ERR_UNSUPPORTED;
@@ -483,14 +556,52 @@ extern "C" int pcfa_corr_ondemand_bwd(void* workspace, const float* coords, cons
   PCFA_LAUNCH_CHECK();
   int st = PCFA_OK;
   switch (radius) {
-    case 1: st = launch_bwd<1>(Lo, workspace, coords, grad_out, accumulate, s); break;
-    case 2: st = launch_bwd<2>(Lo, workspace, coords, grad_out, accumulate, s); break;
-    case 3: st = launch_bwd<3>(Lo, workspace, coords, grad_out, accumulate, s); break;
-    case 4: st = launch_bwd<4>(Lo, workspace, coords, grad_out, accumulate, s); break;
+    case 1: st = launch_bwd<1>(Lo, workspace, coords, grad_out, accumulate, tiled, s); break;
+    case 2: st = launch_bwd<2>(Lo, workspace, coords, grad_out, accumulate, tiled, s); break;
+    case 3: st = launch_bwd<3>(Lo, workspace, coords, grad_out, accumulate, tiled, s); break;
+    case 4: st = launch_bwd<4>(Lo, workspace, coords, grad_out, accumulate, tiled, s); break;
   }
   if (st != PCFA_OK) return st;
   pcfa_launch(od_convert_kernel, dim3(stride_grid(nacc)), dim3(256), 0, s, acc, at<float>(workspace, Lo.o_df2), nacc,
               (const int*)at<int>(workspace, Lo.o_shift), accumulate);
+  PCFA_LAUNCH_CHECK();
+  return PCFA_OK;
+}
+}  // namespace
+
+extern "C" int pcfa_corr_ondemand_fwd(const void* workspace, const float* coords, float* out, int B, int D, int H, int W,
+                                      int num_levels, int radius, void* stream) {
+  return od_fwd(workspace, coords, out, B, D, H, W, num_levels, radius, false, stream);
+}
+
+extern "C" int pcfa_corr_ondemand_fwd_tiled(const void* workspace, const float* coords, float* out, int B, int D, int H,
+                                            int W, int num_levels, int radius, void* stream) {
+  return od_fwd(workspace, coords, out, B, D, H, W, num_levels, radius, true, stream);
+}
+
+extern "C" int pcfa_corr_ondemand_bwd(void* workspace, const float* coords, const float* grad_out, int accumulate, int B,
+                                      int D, int H, int W, int num_levels, int radius, void* stream) {
+  return od_bwd(workspace, coords, grad_out, accumulate, B, D, H, W, num_levels, radius, false, stream);
+}
+
+extern "C" int pcfa_corr_ondemand_bwd_tiled(void* workspace, const float* coords, const float* grad_out, int accumulate,
+                                            int B, int D, int H, int W, int num_levels, int radius, void* stream) {
+  return od_bwd(workspace, coords, grad_out, accumulate, B, D, H, W, num_levels, radius, true, stream);
+}
+
+extern "C" int pcfa_corr_ondemand_tile_geometry(int* tile_w, int* tile_h, int* max_positions) {
+  if (!tile_w || !tile_h || !max_positions) return PCFA_ERR_INVALID_ARG;
+  *tile_w = OD_TW; *tile_h = OD_TH; *max_positions = OD_MAXP;
+  return PCFA_OK;
+}
+
+extern "C" int pcfa_corr_ondemand_tile_routes(const void* workspace, int B, int D, int H, int W, int num_levels,
+                                              int* counts, void* stream) {
+  OdLayout Lo;
+  if (!workspace || !counts) return PCFA_ERR_INVALID_ARG;
+  if (!make_od_layout(Lo, B, D, H, W, num_levels)) return PCFA_ERR_UNSUPPORTED;
+  pcfa_launch(od_routes_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, at<OdTile>(workspace, Lo.o_tab),
+              (long long)B * od_tiles(Lo), num_levels, counts);
   PCFA_LAUNCH_CHECK();
   return PCFA_OK;
 }

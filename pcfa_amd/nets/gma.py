@@ -204,7 +204,8 @@ class RAFTGMA(nn.Module):
 
         fmap1, fmap2 = self.fnet(images12, split=image1.shape[0])
         if cfg(self).corr == "on_demand":   # O(Q*D) correlation; the attention below is O(Q^2) unless gma_attention = "streamed"
-            corr_fn = ops.get().OnDemandCorrBlock(_f32(fmap1), _f32(fmap2), num_levels=4, radius=self.args.corr_radius)
+            corr_fn = ops.get().OnDemandCorrBlock(_f32(fmap1), _f32(fmap2), num_levels=4, radius=self.args.corr_radius,
+                                                  lookup=cfg(self).ondemand_lookup)
         else:
             corr_fn = ops.get().CorrBlock(_f32(fmap1), _f32(fmap2), num_levels=4, radius=self.args.corr_radius,
                                           bwd_windows=cfg(self).pyramid_bwd_windows, **mfma_kw(cfg(self)))

@@ -555,7 +555,7 @@ class RAFT(nn.Module):
         fmap1, fmap2 = self.fnet(images12, split=image1.shape[0])
         if cfg(self).corr == "on_demand":
             corr_fn = ops.get().OnDemandCorrBlock(_f32(fmap1), _f32(fmap2), num_levels=self.args["corr_levels"],
-                                                  radius=self.args["corr_radius"])
+                                                  radius=self.args["corr_radius"], lookup=cfg(self).ondemand_lookup)
         else:
             corr_fn = ops.get().CorrBlock(_f32(fmap1), _f32(fmap2), num_levels=self.args["corr_levels"],
                                           radius=self.args["corr_radius"], bwd_windows=cfg(self).pyramid_bwd_windows,

@@ -231,7 +231,7 @@ class CorrBlock:
 # --------------------------------------------------------------------------- #
 class _OnDemandState:
     """The build's workspace (include/pcfa_hip.h pcfa_corr_ondemand_*): features, pooled fmap2 pyramid, accumulators."""
-    __slots__ = ("B", "D", "H", "W", "L", "r", "ws", "token_grad", "accumulating")
+    __slots__ = ("B", "D", "H", "W", "L", "r", "ws", "token_grad", "accumulating", "suffix")
 
 
 class _OnDemandBuild(torch.autograd.Function):
@@ -273,7 +273,7 @@ class _OnDemandLookup(torch.autograd.Function):
         c = coords.contiguous()
         n1 = 2 * st.r + 1
         out = torch.empty((st.B, st.L * n1 * n1, st.H, st.W), device=c.device, dtype=torch.float32)
-        _call("pcfa_corr_ondemand_fwd", _ptr(st.ws), _ptr(c), _ptr(out), st.B, st.D, st.H, st.W, st.L, st.r)
+        _call("pcfa_corr_ondemand_fwd" + st.suffix, _ptr(st.ws), _ptr(c), _ptr(out), st.B, st.D, st.H, st.W, st.L, st.r)
         ctx.state = st
         ctx.save_for_backward(c)
         return out
@@ -283,7 +283,7 @@ class _OnDemandLookup(torch.autograd.Function):
         st = ctx.state
         (c,) = ctx.saved_tensors
         g = grad_out.contiguous()
-        _call("pcfa_corr_ondemand_bwd", _ptr(st.ws), _ptr(c), _ptr(g), int(st.accumulating), st.B, st.D, st.H, st.W,
+        _call("pcfa_corr_ondemand_bwd" + st.suffix, _ptr(st.ws), _ptr(c), _ptr(g), int(st.accumulating), st.B, st.D, st.H, st.W,
               st.L, st.r)
         st.accumulating = True
         return _token_grad(st, g.device), None, None
@@ -292,10 +292,15 @@ class _OnDemandLookup(torch.autograd.Function):
 class OnDemandCorrBlock:
     """CorrBlock's constructor and __call__ without the all-pairs pyramid: every lookup computes its (2r+2)^2 window dot
     products against the pooled fmap2 (the reference's AlternateCorrBlock, models/raft/corr.py:63-91).  Memory O(Q*D)
-    per build instead of O(Q^2); same values up to fp32 rounding; deterministic backward."""
+    per build instead of O(Q^2); same values up to fp32 rounding; deterministic backward.
 
-    def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
+    lookup (Config.ondemand_lookup): "per_query" | "tiled" (pcfa_corr_ondemand_fwd_tiled / _bwd_tiled: query tiles with a
+    small common box on the matrix cores, the rest on the per-query kernels)."""
+
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4, lookup="per_query"):
         _dev(fmap1, fmap2)
+        if lookup not in ("per_query", "tiled"):
+            raise ValueError("OnDemandCorrBlock: lookup must be 'per_query' or 'tiled', got %r" % (lookup,))
         if fmap1.shape != fmap2.shape or fmap1.dim() != 4:
             raise ValueError("OnDemandCorrBlock expects two [B,D,H,W] feature maps of equal shape")
         lib = _hip.load()
@@ -311,6 +316,7 @@ class OnDemandCorrBlock:
                              % (st.D, num_levels, radius))
         st.token_grad = None
         st.accumulating = False
+        st.suffix = "_tiled" if lookup == "tiled" else ""
         self._state = st
         self._token = _OnDemandBuild.apply(fmap1, fmap2, st)
 
