@@ -398,6 +398,18 @@ PCFA_API int pcfa_extract_deltas_joint_bwd(const float* nw_delta, const float* i
                                   const float* images_min, const float* grad_delta,
                                   float* grad_nw_delta, long long n, void* stream);
 
+/* One I-FGSM iteration on both images, in place, in ONE launch (attack_FGSM.py:21-56 with clipping, then :208-209):
+ *   s_i  = sign(g_i)                      joint == 0
+ *   s_i  = sign(0.5f * (g1 + g2))         joint == 1 (the fp32 sum is rounded first; inf - inf = NaN moves nothing)
+ *   x_i <- clamp(x_i - epsilon * s_i, 0, 1)      d_i = clamp(x_i, 0, 1) - img_i   (from the updated x_i)
+ * sign is torch's (0 for +-0 and NaN), the clamp keeps NaN; bit-identical to the torch sequence on the GPU.  All arrays hold
+ * n floats (n == 0: nothing is launched; n need not be a multiple of 4); 16-byte accesses where all eight pointers are
+ * 16-byte aligned, scalar accesses otherwise.  g1 / g2 / img1 / img2 are only read.  pcfa_fgsm_step_max_threads(): the most
+ * threads one launch starts -- each handles one float4 (aligned) or one float per trip of its grid-stride loop. */
+PCFA_API int pcfa_fgsm_step(float* x1, float* x2, const float* g1, const float* g2, const float* img1, const float* img2,
+                            float* d1, float* d2, float epsilon, int joint, long long n, void* stream);
+PCFA_API int pcfa_fgsm_step_max_threads(void);
+
 /* loss_delta_constraint (helper_functions/losses.py:200-230) =
  *   get_loss(f_type, pred, target) + mu * relu((|d1|^2+|d2|^2)/(n1+n2) - bound^2)
  * pred/target: [B][2][H][W] views given by element strides (sb,sc,sh,sw) so the

@@ -91,6 +91,8 @@ SIGNATURES = {
     "pcfa_extract_deltas_bwd": (c_int, [_P, _P, _P, c_longlong, c_int, c_double, _P]),
     "pcfa_extract_deltas_joint_fwd": (c_int, [_P, _P, _P, _P, c_longlong, _P]),
     "pcfa_extract_deltas_joint_bwd": (c_int, [_P, _P, _P, _P, _P, c_longlong, _P]),
+    "pcfa_fgsm_step": (c_int, [_P] * 8 + [c_float, c_int, c_longlong, _P]),
+    "pcfa_fgsm_step_max_threads": (c_int, []),
     "pcfa_flow_loss_workspace_bytes": (c_size_t, []),
     "pcfa_flow_loss_fwd": (c_int, [_P, _S4, _P, _S4, c_int, c_int, c_int, _P, c_longlong, _P, c_longlong,
                                    c_float, c_float, c_int, _P, _P, _P]),

@@ -639,3 +639,100 @@ extern "C" int pcfa_sum_squares(const float* x, long long n, float* out, void* w
   PCFA_LAUNCH_CHECK();
   return PCFA_OK;
 }
+
+// ---------------------------------------------------------------- I-FGSM step (attack_FGSM.py:21-56, :208-209)
+// One launch per iteration, in place: x_i <- clamp(x_i - epsilon * s_i, 0, 1), d_i = clamp(x_i, 0, 1) - img_i from the
+// UPDATED x_i, with s_i = sign(g_i) (disjoint) or sign(0.5 * (g1 + g2)) for both images (joint).  Replaces the ~14 ATen
+// element-wise launches of fgsm_attack_step(..., clipping=True) + clamp + subtract and reproduces them bit for bit: every
+// operation below is ONE fp32 rounding in ATen's order (the explicit *_rn intrinsics keep the compiler from contracting or
+// reassociating anything).
+namespace {
+
+constexpr int FGSM_THREADS = 256;
+constexpr int FGSM_MAX_BLOCKS = 2048;
+
+// torch.sign: -1, 0 or 1; 0 for +-0 and for NaN (both comparisons are false), +-1 for subnormals and +-inf
+__device__ __forceinline__ float fgsm_sign(float g) { return (float)((0.f < g) - (g < 0.f)); }
+
+// torch.clamp(v, 0, 1) on the GPU: NaN goes through, everything else through max then min (ATen's own expression, so a
+// signed zero comes out as it does there); fminf / fmaxf alone would turn a NaN pixel into 0
+__device__ __forceinline__ float fgsm_clamp01(float v) { return v != v ? v : fminf(fmaxf(v, 0.f), 1.f); }
+
+__device__ __forceinline__ void fgsm_one(float x1, float x2, float g1, float g2, float i1, float i2, float eps, int joint,
+                                         float& y1, float& y2, float& d1, float& d2) {
+  float s1, s2;
+  if (joint) {
+    s1 = s2 = fgsm_sign(__fmul_rn(0.5f, __fadd_rn(g1, g2)));   // the sum is rounded (and may overflow) first
+  } else {
+    s1 = fgsm_sign(g1);
+    s2 = fgsm_sign(g2);
+  }
+  y1 = fgsm_clamp01(__fsub_rn(x1, __fmul_rn(eps, s1)));
+  y2 = fgsm_clamp01(__fsub_rn(x2, __fmul_rn(eps, s2)));
+  d1 = __fsub_rn(fgsm_clamp01(y1), i1);   // (the second clamp is the identity on a clamped value, NaN included)
+  d2 = __fsub_rn(fgsm_clamp01(y2), i2);
+}
+
+// VEC: every pointer is 16-byte aligned -> n / 4 float4 items grid-stride, then the n % 4 tail elements one per thread of
+// the first workgroup.  !VEC: one float per thread and trip.
+template <bool VEC>
+__global__ __launch_bounds__(FGSM_THREADS) void fgsm_step_kernel(float* x1, float* x2, const float* __restrict__ g1,
+                                                                 const float* __restrict__ g2,
+                                                                 const float* __restrict__ img1,
+                                                                 const float* __restrict__ img2, float* __restrict__ d1,
+                                                                 float* __restrict__ d2, float eps, int joint, long long n) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  long long tail = 0;
+  if (VEC) {
+    const long long n4 = n >> 2;
+    tail = n4 << 2;
+    for (long long i = gid; i < n4; i += stride) {
+      const float4 a1 = reinterpret_cast<const float4*>(x1)[i], a2 = reinterpret_cast<const float4*>(x2)[i];
+      const float4 b1 = reinterpret_cast<const float4*>(g1)[i], b2 = reinterpret_cast<const float4*>(g2)[i];
+      const float4 c1 = reinterpret_cast<const float4*>(img1)[i], c2 = reinterpret_cast<const float4*>(img2)[i];
+      float4 y1, y2, e1, e2;
+      fgsm_one(a1.x, a2.x, b1.x, b2.x, c1.x, c2.x, eps, joint, y1.x, y2.x, e1.x, e2.x);
+      fgsm_one(a1.y, a2.y, b1.y, b2.y, c1.y, c2.y, eps, joint, y1.y, y2.y, e1.y, e2.y);
+      fgsm_one(a1.z, a2.z, b1.z, b2.z, c1.z, c2.z, eps, joint, y1.z, y2.z, e1.z, e2.z);
+      fgsm_one(a1.w, a2.w, b1.w, b2.w, c1.w, c2.w, eps, joint, y1.w, y2.w, e1.w, e2.w);
+      reinterpret_cast<float4*>(x1)[i] = y1;
+      reinterpret_cast<float4*>(x2)[i] = y2;
+      reinterpret_cast<float4*>(d1)[i] = e1;
+      reinterpret_cast<float4*>(d2)[i] = e2;
+    }
+  }
+  for (long long i = tail + gid; i < n; i += stride) {
+    float y1, y2, e1, e2;
+    fgsm_one(x1[i], x2[i], g1[i], g2[i], img1[i], img2[i], eps, joint, y1, y2, e1, e2);
+    x1[i] = y1;
+    x2[i] = y2;
+    d1[i] = e1;
+    d2[i] = e2;
+  }
+}
+
+}  // namespace
+
+extern "C" int pcfa_fgsm_step_max_threads(void) { return FGSM_MAX_BLOCKS * FGSM_THREADS; }
+
+extern "C" int pcfa_fgsm_step(float* x1, float* x2, const float* g1, const float* g2, const float* img1, const float* img2,
+                              float* d1, float* d2, float epsilon, int joint, long long n, void* stream) {
+  if (!x1 || !x2 || !g1 || !g2 || !img1 || !img2 || !d1 || !d2 || n < 0 || (joint != 0 && joint != 1))
+    return PCFA_ERR_INVALID_ARG;
+  if (n == 0) return PCFA_OK;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(x1) | reinterpret_cast<uintptr_t>(x2) | reinterpret_cast<uintptr_t>(g1) |
+                         reinterpret_cast<uintptr_t>(g2) | reinterpret_cast<uintptr_t>(img1) |
+                         reinterpret_cast<uintptr_t>(img2) | reinterpret_cast<uintptr_t>(d1) | reinterpret_cast<uintptr_t>(d2);
+  const bool vec = (bits & 15) == 0 && n >= 4;
+  long long blocks = ((vec ? (n + 3) / 4 : n) + FGSM_THREADS - 1) / FGSM_THREADS;
+  if (blocks > FGSM_MAX_BLOCKS) blocks = FGSM_MAX_BLOCKS;
+  if (vec)
+    pcfa_launch(fgsm_step_kernel<true>, dim3((unsigned)blocks), dim3(FGSM_THREADS), 0, (hipStream_t)stream, x1, x2, g1, g2,
+                img1, img2, d1, d2, epsilon, joint, n);
+  else
+    pcfa_launch(fgsm_step_kernel<false>, dim3((unsigned)blocks), dim3(FGSM_THREADS), 0, (hipStream_t)stream, x1, x2, g1, g2,
+                img1, img2, d1, d2, epsilon, joint, n);
+  PCFA_LAUNCH_CHECK();
+  return PCFA_OK;
+}

@@ -192,3 +192,65 @@ class SplitGraphedClosure:
             p.grad = g
         self.replays += 1
         return self.loss_value
+
+
+class SplitGraphedStep:
+    """SplitGraphedClosure's two graphs with the LOSS on the backward side: F = forward_fn() with autograd recording on,
+    B = loss_fn(out) + backward, sharing one memory pool and one capture stream.
+
+    For the I-FGSM loop (attack_FGSM.FgsmAttack): the target is chosen from the prediction of the very first forward, so
+    the loss cannot be part of that forward; and every iteration is backward at x_i / step / forward at x_{i+1}, i.e.
+    `backward()`, an in-place update of `params` by the caller, `forward()` -- steps + 1 forwards and steps backwards for
+    steps iterations, the kernels of the eager loop in the eager loop's order.  Nothing here writes to `params`: the warm-up
+    runs leave them where they were.
+
+    forward_fn() -> (out, aux): `out` is what loss_fn differentiates, `aux` any structure of tensors computed next to it
+    (metrics); both are static outputs.  loss_fn(out) -> scalar loss."""
+
+    def __init__(self, forward_fn, loss_fn, params, warmup=2):
+        self.params = list(params)
+        dev = self.params[0].device
+        cur = torch.cuda.current_stream(dev)
+        side = _core.new_stream(dev)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                for p in self.params:
+                    p.grad = None
+                out, _ = forward_fn()
+                loss = loss_fn(out)
+                loss.backward()
+                del loss, out
+        cur.wait_stream(side)
+        torch.cuda.synchronize(dev)
+        _core.release_stream(side)
+        for p in self.params:
+            p.grad = None
+        pool = torch.cuda.graph_pool_handle()
+        self.fwd_graph, self.bwd_graph = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        cap = self._capture_stream = _core.new_stream(dev)   # ONE stream for both graphs (as SplitGraphedClosure)
+        with _no_gc():
+            with torch.cuda.graph(self.fwd_graph, pool=pool, stream=cap):
+                self.out, self.aux = forward_fn()
+            with torch.cuda.graph(self.bwd_graph, pool=pool, stream=cap):
+                self.loss = loss_fn(self.out)
+                self.loss.backward()
+        self.grads = [p.grad for p in self.params]
+        self.loss_value = self.loss.detach()
+        self.forwards = self.backwards = 0
+
+    def forward(self):
+        self.fwd_graph.replay()
+        self.forwards += 1
+        return self.out, self.aux
+
+    def backward(self):
+        """Gradients of the loss at the point of the last forward(); returned in the order of `params`."""
+        self.bwd_graph.replay()
+        for p, g in zip(self.params, self.grads):
+            p.grad = g
+        self.backwards += 1
+        return self.grads
+
+    def __del__(self):
+        _release(getattr(self, "_capture_stream", None))

@@ -40,6 +40,8 @@ _FLAGS = [
                                                   help="one perturbation shared by both frames"), _ALWAYS),
     ("perturbation", "--steps", dict(default=20, type=int, help="optimisation steps per pair"), _ALWAYS),
     ("fgsm", "--epsilon", dict(default=0.00025, type=float, help="I-FGSM step size"), _FGSM),
+    ("fgsm", "--pairs_in_flight", dict(default=1, type=int, help="NEW: independent pairs attacked side by side on every "
+                                       "GPU (results identical to 1)"), _FGSM),
     ("pcfa", "--universal_perturbation", dict(action='store_true', default=False,
                                               help="one perturbation for the whole dataset"), _PCFA),
     ("pcfa", "--boxconstraint", dict(default='change_of_variables', choices=['clipping', 'change_of_variables'],

@@ -146,6 +146,20 @@ def extract_deltas_joint(nw_delta, images_max, images_min):
     return delta, delta
 
 
+def fgsm_step(x1, x2, g1, g2, image1, image2, d1, d2, epsilon, joint):
+    """One I-FGSM iteration in ONE launch, in place (attack_FGSM.py:21-56 with clipping + :208-209): x_i moves by
+    -epsilon * sign(gradient) and is clamped to [0, 1]; d_i = clamp(x_i, 0, 1) - image_i is written from the updated x_i.
+    Bit-identical to fgsm_attack_step + clamp + subtract.  No autograd: the caller updates leaf variables between a
+    backward and the next forward.  All eight tensors are dense (views of larger buffers are fine) and of one size."""
+    ts = (x1, x2, g1, g2, image1, image2, d1, d2)
+    _dev(*ts)
+    n = x1.numel()
+    for t in ts:
+        if t.numel() != n or not t.is_contiguous():
+            raise ValueError("fgsm_step: eight dense tensors of one size, got %s" % [tuple(t_.shape) for t_ in ts])
+    _call("pcfa_fgsm_step", *[_ptr(t) for t in ts], float(epsilon), int(bool(joint)), n)
+
+
 _WS = {}
 
 

@@ -21,6 +21,7 @@ Operator boundaries mirrored (reference file:line) -- one module per group:
   spynet       conv7x7, spynet_warp                        models/SpyNet/SpyNet.py:56-102 (Config.spynet_ops = "hip")
   attack_math  box_transform, extract_deltas(_joint), loss_delta_constraint, avg_epe, two_norm_*, pm1_pair
                                                               helper_functions/own_models.py:62-85, attack_PCFA.py:20-37, losses.py
+               fgsm_step                                      attack_FGSM.py:21-56,208-209
 """
 from .. import _hip  # noqa: F401
 from ..lbfgs import LBFGS  # noqa: F401  (the attack loop's optimiser: torch.optim.LBFGS semantics, HIP vector math)
