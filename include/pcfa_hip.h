@@ -598,6 +598,21 @@ PCFA_API size_t pcfa_conv3x3_workspace_bytes(int B, int K, int N, int H, int W);
 PCFA_API int pcfa_conv3x3_run(const float* x, const float* packed, const float* bias, const float* mask,
                      const float* addend, float* out, int B, int K, int N, int H, int W, int act, float slope,
                      int mask_channels, void* workspace, size_t workspace_bytes, void* stream);
+/* The same operator over images that are channel prefixes of wider slabs: image b of x / mask / addend / out starts
+ * `*_img_stride` ELEMENTS behind image b - 1, each stride at least channels * H * W (K for x, N for the others;
+ * PCFA_ERR_INVALID_ARG otherwise; the strides of NULL tensors are ignored).  Image offsets are 64-bit; alignment as
+ * pcfa_conv3x3_run (only `packed`: 16 B).  Serves the direct F(2x2,3x3) launch only: where pcfa_conv3x3_run's rules pick
+ * F(4x4,3x3) or K slices for (B, K, N, H, W) -- neither happens for B > 2 -- or for ONE such image (1, K, N, H, W), it
+ * returns PCFA_ERR_UNSUPPORTED and the caller runs pcfa_conv3x3_run per image.  `workspace` is not used.  The kernel
+ * instance is the one pcfa_conv3x3_run launches for one image alone, so every image's result is bit-identical to that
+ * call on a dense copy of the image.
+ * N is the number of output channels COMPUTED.  The packing is 32-channel-block-major, so a prefix of it is valid: with
+ * `packed` = pack(K, N_full) and N < N_full the call computes and writes channels [0, N) only, bit-identical to the first N
+ * channels of the N_full result; channels >= N of the out slab are not touched. */
+PCFA_API int pcfa_conv3x3_run_strided(const float* x, long long x_img_stride, const float* packed, const float* bias,
+                     const float* mask, long long mask_img_stride, const float* addend, long long addend_img_stride,
+                     float* out, long long out_img_stride, int B, int K, int N, int H, int W, int act, float slope,
+                     int mask_channels, void* workspace, size_t workspace_bytes, void* stream);
 
 /* out = relu(x + bias[c]) and its backward gx = grad_out * (out > 0): the "conv -> +bias -> ReLU" tail of the
  * motion encoder / flow head convolutions (models/raft/update.py:12-16,91-101) in one pass. */

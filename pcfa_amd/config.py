@@ -37,6 +37,10 @@ class Config:
     ondemand_lookup: str = "per_query"   # execution of corr="on_demand"'s lookups: "per_query" (one wave per query) | "tiled" (8x8
                                          # query tiles whose windows share a small box run on the fp32 matrix cores, one
                                          # fixed-point scatter per box element; wide tiles keep the per-query kernels)
+    motion_bwd: str = "batched"          # backward of RAFT's motion encoder: "batched" (its two 3x3 data gradients once per closure
+                                         # over all refinement iterations, ops.motion_steps; frozen weights, one image, fused
+                                         # all-pairs lookup -- anything else runs "per_iteration") | "per_iteration" (one pair of
+                                         # launches per iteration, interleaved with the GRU backward); bit-identical results
     mfma: str = "f32"                    # arithmetic of the hand-written GEMM core: "f32" (v_mfma_f32_32x32x2_f32) | "bf16x3" (each
                                          # fp32 operand split into three bf16 pieces, six v_mfma_f32_32x32x16_bf16 products: fp32
                                          # accuracy at 16/6 of the fp32 matrix roof).  Takes effect where that core runs: the
@@ -73,6 +77,7 @@ class Config:
                    conv1x1=os.environ.get("PCFA_CONV1X1", "lib"),
                    corr=os.environ.get("PCFA_CORR", "all_pairs"),
                    ondemand_lookup=os.environ.get("PCFA_ONDEMAND_LOOKUP", "per_query"),
+                   motion_bwd=os.environ.get("PCFA_MOTION_BWD", "batched"),
                    mfma=os.environ.get("PCFA_MFMA", "f32"),
                    spynet_ops=os.environ.get("PCFA_SPYNET_OPS", "lib"),
                    flownet2_ops=os.environ.get("PCFA_FLOWNET2_OPS", "lib"),
@@ -89,6 +94,8 @@ class Config:
             raise ValueError("Config.corr must be 'all_pairs' or 'on_demand', got %r" % (self.corr,))
         if self.ondemand_lookup not in ("per_query", "tiled"):
             raise ValueError("Config.ondemand_lookup must be 'per_query' or 'tiled', got %r" % (self.ondemand_lookup,))
+        if self.motion_bwd not in ("batched", "per_iteration"):
+            raise ValueError("Config.motion_bwd must be 'batched' or 'per_iteration', got %r" % (self.motion_bwd,))
         if self.mfma not in ("f32", "bf16x3"):
             raise ValueError("Config.mfma must be 'f32' or 'bf16x3', got %r" % (self.mfma,))
         if self.spynet_ops not in ("lib", "hip"):

@@ -115,6 +115,10 @@ struct Second {
   int cper;     // and writes its raw sums to out[(s * images + image)] -- a partial output for f43_finish_kernel (small
                 // maps: a handful of workgroups walking the whole K is a latency chain of ~1 us per chunk)
   PcfaXcdMap xcd;   // a != 0: 1-D grid, XCD k owns a sub-rectangle of (tile block, channel block) (common.hpp)
+  // per-image element strides of x / out / mask / addend (the FIRST problem; a second problem is one image).  Dense:
+  // K plane, N plane, N plane, N plane; larger where the images are channel prefixes of wider slabs
+  // (pcfa_conv3x3_run_strided).  The image offset is 64-bit, offsets inside an image stay 32-bit.
+  long long x_img, out_img, mask_img, addend_img;
 };
 
 // KS = 2: in-workgroup split-K for launches of at most one workgroup per CU (e.g. conv 256 -> 126 at 55x128: 224
@@ -169,10 +173,10 @@ __global__ __launch_bounds__(256 * MT * KS) __attribute__((amdgpu_waves_per_eu(K
   if (n0 >= N) return;  // (the packing pads N to 64: a 32-channel block may lie entirely in the padding)
   const long long plane = (long long)H * W;
   const int ksl = second.ksl, img = blockIdx.z / ksl, slice = blockIdx.z - img * ksl;   // ksl = 1: img = blockIdx.z
-  x += (long long)img * K * plane;
-  out += ((long long)slice * (gridDim.z / ksl) + img) * N * plane;
-  if (mask != nullptr) mask += (long long)img * N * plane;   // same shape as `out`
-  if (addend != nullptr) addend += (long long)img * N * plane;
+  x += (long long)img * second.x_img;
+  out += ((long long)slice * (gridDim.z / ksl) + img) * second.out_img;
+  if (mask != nullptr) mask += (long long)img * second.mask_img;   // same channels and size as `out`
+  if (addend != nullptr) addend += (long long)img * second.addend_img;
 
   // ---- per-thread constants of the staging loads (chunk-invariant) ----
   unsigned praw[RAW_LOADS];      // chunk 0 source of the patch element (clamped into the image), floats from x
@@ -516,7 +520,8 @@ extern "C" int pcfa_leaky_relu_bwd(const float* out, const float* grad_out, floa
 static int conv3x3_launch(const float* x, const float* packed, const float* bias, const float* mask, float* out, int B,
                           int K, int N, int H, int W, int act, float slope, void* stream, const float* x2 = nullptr,
                           const float* packed2 = nullptr, const float* bias2 = nullptr, float* out2 = nullptr,
-                          int K2 = 0, int N2 = 0, const float* addend = nullptr, int mask_n = 0, int ksl = 1);
+                          int K2 = 0, int N2 = 0, const float* addend = nullptr, int mask_n = 0, int ksl = 1,
+                          const long long* img_strides = nullptr);
 
 extern "C" int pcfa_conv3x3_fwd(const float* x, const float* packed, const float* bias, float* out, int B, int K,
                                 int N, int H, int W, int relu, void* stream) {
@@ -647,10 +652,36 @@ extern "C" int pcfa_conv3x3_run(const float* x, const float* packed, const float
                         nullptr, 0, 0, addend, mask_channels);
 }
 
+// pcfa_conv3x3_run's direct F(2x2,3x3) launch over images that sit `*_img_stride` elements apart: channel prefixes of wider
+// slabs (K of the x slab's channels, N of the out / mask / addend slabs' channels).  The packing is 32-channel-block-major,
+// so N may also be a prefix of the packing's output channels: only those are computed and written.
+extern "C" int pcfa_conv3x3_run_strided(const float* x, long long x_img_stride, const float* packed, const float* bias,
+                                        const float* mask, long long mask_img_stride, const float* addend,
+                                        long long addend_img_stride, float* out, long long out_img_stride, int B, int K,
+                                        int N, int H, int W, int act, float slope, int mask_channels, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+  (void)workspace;
+  (void)workspace_bytes;   // (the direct launch needs none: the parameters mirror pcfa_conv3x3_run)
+  if (!x || !packed || !out || B < 1 || K < 1 || N < 1 || H < 1 || W < 1 || act < 0 || act > 2 || mask_channels < 0 ||
+      mask_channels > N || (mask_channels > 0 && (!mask || act != 0)) || (mask && act == 2))
+    return PCFA_ERR_INVALID_ARG;
+  const long long plane = (long long)H * W;
+  if (x_img_stride < K * plane || out_img_stride < N * plane || (mask && mask_img_stride < N * plane) ||
+      (addend && addend_img_stride < N * plane))
+    return PCFA_ERR_INVALID_ARG;
+  // the rules of the call's batch AND of one image alone: the launch below then forms every image's sums exactly as
+  // pcfa_conv3x3_run does for that image on its own (conv3x3_launch picks the in-workgroup split-K per image too)
+  if (use_f43(B, K, N, H, W) || f23_kslices(B, K, N, H, W) > 1 || use_f43(1, K, N, H, W) || f23_kslices(1, K, N, H, W) > 1)
+    return PCFA_ERR_UNSUPPORTED;
+  const long long strides[4] = {x_img_stride, out_img_stride, mask ? mask_img_stride : 0, addend ? addend_img_stride : 0};
+  return conv3x3_launch(x, packed, bias, mask, out, B, K, N, H, W, act, slope, stream, nullptr, nullptr, nullptr, nullptr,
+                        0, 0, addend, mask_channels, 1, strides);
+}
+
 static int conv3x3_launch(const float* x, const float* packed, const float* bias, const float* mask, float* out, int B,
                           int K, int N, int H, int W, int act, float slope, void* stream, const float* x2,
                           const float* packed2, const float* bias2, float* out2, int K2, int N2, const float* addend,
-                          int mask_n, int ksl) {
+                          int mask_n, int ksl, const long long* img_strides) {
   if (act < 0 || act > 2 || mask_n < 0 || (mask_n > 0 && (act != 0 || !mask))) return PCFA_ERR_INVALID_ARG;
   if (!x || !packed || !out || B < 1 || K < 1 || N < 1 || H < 1 || W < 1 || !aligned16(packed))
     return PCFA_ERR_INVALID_ARG;
@@ -680,7 +711,12 @@ static int conv3x3_launch(const float* x, const float* packed, const float* bias
     grid.z = (unsigned)(B * ksl);
     if (grid.z > 65535) return PCFA_ERR_UNSUPPORTED;
   }
-  Second second{x2, packed2, bias2, out2, K2, N2, (int)grid.y, mask_n, ksl, cper, PcfaXcdMap{0, 0, 0, 0}};
+  // img_strides = {x, out, mask, addend} elements per image; nullptr: dense
+  const long long dense_x = (long long)K * H * W, dense_n = (long long)N * H * W;
+  Second second{x2, packed2, bias2, out2, K2, N2, (int)grid.y, mask_n, ksl, cper, PcfaXcdMap{0, 0, 0, 0},
+                img_strides ? img_strides[0] : dense_x, img_strides ? img_strides[1] : dense_n,
+                img_strides ? img_strides[2] : dense_n, img_strides ? img_strides[3] : dense_n};
+  if (img_strides != nullptr && (ksl > 1 || x2 != nullptr)) return PCFA_ERR_INVALID_ARG;   // (partial outputs are dense)
   if (x2 != nullptr) {
     grid.y += (unsigned)((N2 + CB - 1) / CB * CB / 32);
     if (grid.y > 65535) return PCFA_ERR_UNSUPPORTED;
@@ -690,8 +726,12 @@ static int conv3x3_launch(const float* x, const float* packed, const float* bias
   // (batch 1); neutral within 1-2 % on the 110x256 and 55x128 maps -- so only grids of >= 1024 workgroups take it.
   // PCFA_XCD_MAP=0: plain 2-D grid (A/B).
   const long long nwg = (long long)grid.x * grid.y * grid.z;   // (live workgroups: the XCD map below pads the grid)
+  // strided images: the split-K rule below looks at ONE image, so that a batch of slab images equals the single-image
+  // calls it replaces
+  const long long nwg_ks = img_strides != nullptr ? nwg / grid.z : nwg;
   static const bool xcd_on = !(getenv("PCFA_XCD_MAP") && atoi(getenv("PCFA_XCD_MAP")) == 0);
-  if (xcd_on && mt == 1 && (long long)grid.x * grid.y >= 1024) {
+  static const long long xcd_min = getenv("PCFA_XCD_MAP_MIN") ? atoll(getenv("PCFA_XCD_MAP_MIN")) : 1024;   // (A/B)
+  if (xcd_on && mt == 1 && (long long)grid.x * grid.y >= xcd_min) {
     second.xcd = pcfa_xcd_pick((int)grid.x, (int)grid.y, 4.0 * K * H * W, 4.0 * 16 * K * 32 * grid.y);
     if (second.xcd.a != 0) {
       grid.x = pcfa_xcd_grid(second.xcd);
@@ -708,7 +748,7 @@ static int conv3x3_launch(const float* x, const float* packed, const float* bias
   const bool kfull = K % KC == 0;
   // at most one workgroup per CU: split K inside the workgroup (8 waves, two per SIMD)
   static const int ks_env = getenv("PCFA_CONV3X3_KS") ? atoi(getenv("PCFA_CONV3X3_KS")) : 0;   // tuning override (1 / 2)
-  if (ksl == 1 && mt == 1 && x2 == nullptr && K % (2 * KC) == 0 && (ks_env ? ks_env == 2 : nwg <= 256)) {
+  if (ksl == 1 && mt == 1 && x2 == nullptr && K % (2 * KC) == 0 && (ks_env ? ks_env == 2 : nwg_ks <= 256)) {
     block.x = 512;
     if (act == 1) pcfa_launch(conv3x3_winograd_kernel<1, 32, 1, true, 2, 2>, PCFA_C3_ARGS);
     else if (act == 2) pcfa_launch(conv3x3_winograd_kernel<2, 32, 1, true, 2, 2>, PCFA_C3_ARGS);

@@ -379,13 +379,15 @@ class SepConvGRU(nn.Module):
         fans = {tag: ops.get().fanout(p, iters) for tag, (_, p) in ctx.items()}
         return [{tag: (ctx[tag][0], fans[tag][i]) for tag in ctx} for i in range(iters)]
 
-    def step(self, h, ctx, rest, rest_relu_channels=0):
+    def step(self, h, ctx, rest, rest_relu_channels=0, d_rest_dst=None):
         """One GRU update given precompute()'s context; `rest` = the per-iteration part of x (motion features).
         rest_relu_channels: see ops.gru_step (the leading channels of `rest` whose ReLU backward this node applies)."""
         # one autograd node per update: sepconv5 reads [h | rest] in place (no torch.cat, no im2col) and the
         # backward accumulates the gradients of h and rest inside the kernels that produce them
-        return ops.get().gru_step(h, rest, tuple(ctx[zr] + ctx[q] for zr, q in (("zr1", "q1"), ("zr2", "q2"))),
-                                  rest_relu_channels)
+        halves = tuple(ctx[zr] + ctx[q] for zr, q in (("zr1", "q1"), ("zr2", "q2")))
+        if d_rest_dst is not None:   # (BasicUpdateBlock.motion_steps: the gradient of `rest` goes into its slab in place)
+            return ops.get().gru_step(h, rest, halves, rest_relu_channels, d_rest_dst=d_rest_dst)
+        return ops.get().gru_step(h, rest, halves, rest_relu_channels)
 
 
 class LookupRef:
@@ -485,14 +487,31 @@ class BasicUpdateBlock(nn.Module):
         self.mask = _mask_head()
         self._mask_cache = {}
 
-    def forward(self, net, inp, corr, flow, want_mask=True, gru_ctx=None):
-        # frozen weights: the GRU node is the motion features' only consumer and differentiates their ReLU itself
-        defer = cfg(self).defer_relu and gru_ctx is not None and self.encoder.can_defer_relu(flow)
-        motion_features = self.encoder(flow, corr, defer_relu=defer)
-        if gru_ctx is not None:   # frozen weights: context-feature part of the gate convolutions hoisted
-            net = self.gru.step(net, gru_ctx, motion_features, self.encoder.RELU_CHANNELS if defer else 0)
+    def motion_steps(self, corr_fn, flow, iters, gru_ctx):
+        """Config.motion_bwd = "batched": the motion encoder of all `iters` iterations as ops.motion_steps (its two 3x3 data
+        gradients run once per backward pass, over all iterations), or None where that does not apply -- the conditions of
+        the deferred ReLU, the fused all-pairs lookup, and an operator table that has it; forward() then runs the layers."""
+        c, enc = cfg(self), self.encoder
+        make = getattr(ops.get(), "motion_steps", None)
+        if (make is None or c.motion_bwd != "batched" or not c.defer_relu or not c.fused_lookup or c.corr == "on_demand"
+                or gru_ctx is None or not flow.is_cuda or not enc.can_defer_relu(flow)):
+            return None
+        return make(corr_fn, iters, *((m.weight, m.bias) for m in (enc.convc1, enc.convc2, enc.convf1, enc.convf2, enc.conv)))
+
+    def forward(self, net, inp, corr, flow, want_mask=True, gru_ctx=None, motion=None):
+        """motion = (motion_steps()'s result, iteration): the motion features come from its slab."""
+        if motion is not None:
+            steps, itr = motion
+            net = self.gru.step(net, gru_ctx, steps.step(itr, corr.coords, flow), self.encoder.RELU_CHANNELS,
+                                d_rest_dst=steps.d_rest_dst(itr))
         else:
-            net = self.gru(net, torch.cat([inp, motion_features], dim=1))
+            # frozen weights: the GRU node is the motion features' only consumer and differentiates their ReLU itself
+            defer = cfg(self).defer_relu and gru_ctx is not None and self.encoder.can_defer_relu(flow)
+            motion_features = self.encoder(flow, corr, defer_relu=defer)
+            if gru_ctx is not None:   # frozen weights: context-feature part of the gate convolutions hoisted
+                net = self.gru.step(net, gru_ctx, motion_features, self.encoder.RELU_CHANNELS if defer else 0)
+            else:
+                net = self.gru(net, torch.cat([inp, motion_features], dim=1))
         delta_flow = self.flow_head(net)
         mask = mask_logits(self.mask, net, self._mask_cache) if want_mask else None
         return net, mask, delta_flow
@@ -579,13 +598,15 @@ class RAFT(nn.Module):
         flow_predictions = []
         flow_up = None
         flow_cur = coords1 - coords0
+        steps = self.update_block.motion_steps(corr_fn, flow_cur, iters, gru_ctx)
         for itr in range(iters):
             coords1 = coords1.detach()  # the lookup gets no coordinate gradient (raft.py:122-123)
             corr = LookupRef(corr_fn, coords1)   # evaluated inside the motion encoder (fused with convc1 where possible)
             flow = flow_cur.detach()             # = coords1 - coords0 of the detached coordinates
             need_up = (not test_mode) or itr == iters - 1
             net, up_mask, delta_flow = self.update_block(net, inp, corr, flow, want_mask=need_up,
-                                                         gru_ctx=None if gru_ctx is None else gru_ctx[itr])
+                                                         gru_ctx=None if gru_ctx is None else gru_ctx[itr],
+                                                         motion=None if steps is None else (steps, itr))
             # coords1 + delta_flow and the new flow in one launch (the reference: an add here, a subtract per use)
             coords1, flow_cur = ops.get().flow_step(coords1, delta_flow, coords0)
             if need_up:

@@ -537,6 +537,38 @@ class _Conv3x3(torch.autograd.Function):
 _PAIR_LAUNCH = os.environ.get("PCFA_CONV3X3_PAIR", "1") != "0"   # A/B switch (tools/dev)
 
 
+def _conv3x3_cat_fill(xs, ws, bs, tails, buf):
+    """The forward launches of conv3x3_cat into `buf` [1, sum of widths, H, W] (contiguous; a slice of a slab will do);
+    returns [(packed data-gradient weights, Cin, Cout, channel offset)] per convolution."""
+    H, W = buf.shape[2:]
+    plane = H * W
+    off, packs, fwds, offs = 0, [], [], []
+    for x, w, b in zip(xs, ws, bs):
+        if tuple(x.shape) != (1, w.shape[1], H, W) or tuple(w.shape[2:]) != (3, 3):
+            raise ValueError("conv3x3_cat: input %s does not fit weight %s" % (tuple(x.shape), tuple(w.shape)))
+        fwd, bwd = _conv3x3_packed(w)
+        fwds.append(fwd)
+        offs.append(off)
+        packs.append((bwd, w.shape[1], w.shape[0], off))
+        off += w.shape[0]
+    lib = _hip.load()
+    f23 = all(lib.pcfa_conv3x3_algo(1, w.shape[1], w.shape[0], H, W) == 23 for w in ws)
+    if len(ws) == 2 and (ws[0].shape[1] % 8 == 0) == (ws[1].shape[1] % 8 == 0) and _PAIR_LAUNCH and f23:
+        # two independent convolutions, one launch: the smaller one's workgroups fill the larger one's last round
+        i, j = (0, 1) if ws[0].shape[0] * ws[0].shape[1] >= ws[1].shape[0] * ws[1].shape[1] else (1, 0)
+        _call("pcfa_conv3x3_act_fwd_pair", _ptr(xs[i]), _ptr(fwds[i]), _ptr(bs[i]), _ptr_off(buf, offs[i] * plane),
+              ws[i].shape[1], ws[i].shape[0], _ptr(xs[j]), _ptr(fwds[j]), _ptr(bs[j]),
+              _ptr_off(buf, offs[j] * plane), ws[j].shape[1], ws[j].shape[0], H, W, 1, 0.)
+    else:
+        for x, w, b, fwd, o_ in zip(xs, ws, bs, fwds, offs):
+            _conv3x3_run(x.device, _ptr(x), fwd, _ptr(b), None, None, _ptr_off(buf, o_ * plane), 1, w.shape[1],
+                         w.shape[0], H, W, 1, 0.)
+    for t in tails:
+        buf[:, off:off + t.shape[1]].copy_(t)
+        off += t.shape[1]
+    return packs
+
+
 class _Conv3x3Cat(torch.autograd.Function):
     """cat([relu(conv3x3(x_i, w_i, b_i)) for i] + tails, dim=1) in one pre-allocated buffer (batch size 1): the
     convolutions write their channel blocks in place, trailing tensors (e.g. the flow of the motion encoder,
@@ -552,33 +584,9 @@ class _Conv3x3Cat(torch.autograd.Function):
         B, _, H, W = xs[0].shape
         if B != 1:
             raise ValueError("conv3x3_cat: batch size 1 only")
-        plane = H * W
         widths = [w.shape[0] for w in ws] + [t.shape[1] for t in tails]
         buf = torch.empty((1, sum(widths), H, W), device=xs[0].device, dtype=torch.float32)
-        off, packs, fwds, offs = 0, [], [], []
-        for x, w, b in zip(xs, ws, bs):
-            if tuple(x.shape) != (1, w.shape[1], H, W) or tuple(w.shape[2:]) != (3, 3):
-                raise ValueError("conv3x3_cat: input %s does not fit weight %s" % (tuple(x.shape), tuple(w.shape)))
-            fwd, bwd = _conv3x3_packed(w)
-            fwds.append(fwd)
-            offs.append(off)
-            packs.append((bwd, w.shape[1], w.shape[0], off))
-            off += w.shape[0]
-        lib = _hip.load()
-        f23 = all(lib.pcfa_conv3x3_algo(1, w.shape[1], w.shape[0], H, W) == 23 for w in ws)
-        if n_conv == 2 and (ws[0].shape[1] % 8 == 0) == (ws[1].shape[1] % 8 == 0) and _PAIR_LAUNCH and f23:
-            # two independent convolutions, one launch: the smaller one's workgroups fill the larger one's last round
-            i, j = (0, 1) if ws[0].shape[0] * ws[0].shape[1] >= ws[1].shape[0] * ws[1].shape[1] else (1, 0)
-            _call("pcfa_conv3x3_act_fwd_pair", _ptr(xs[i]), _ptr(fwds[i]), _ptr(bs[i]), _ptr_off(buf, offs[i] * plane),
-                  ws[i].shape[1], ws[i].shape[0], _ptr(xs[j]), _ptr(fwds[j]), _ptr(bs[j]),
-                  _ptr_off(buf, offs[j] * plane), ws[j].shape[1], ws[j].shape[0], H, W, 1, 0.)
-        else:
-            for x, w, b, fwd, o_ in zip(xs, ws, bs, fwds, offs):
-                _conv3x3_run(x.device, _ptr(x), fwd, _ptr(b), None, None, _ptr_off(buf, o_ * plane), 1, w.shape[1],
-                             w.shape[0], H, W, 1, 0.)
-        for t in tails:
-            buf[:, off:off + t.shape[1]].copy_(t)
-            off += t.shape[1]
+        packs = _conv3x3_cat_fill(xs, ws, bs, tails, buf)
         ctx.packs, ctx.dims, ctx.n_conv, ctx.tail_widths = packs, (H, W), n_conv, [t.shape[1] for t in tails]
         ctx.save_for_backward(buf, *(xs if ctx.mask_input_grads else ()))
         return buf

@@ -8,6 +8,7 @@ import torch
 
 from .. import _hip
 from . import core
+from .conv import FEWIN_SHAPES, _conv3x3_cat_fill, _conv3x3_packed, _conv3x3_run, conv_fewin
 from .core import _call, _dev, _note_work, _pair, _ptr, _ptr_off, _stream, cached_pack
 
 
@@ -174,6 +175,171 @@ class _CorrLookupConv(torch.autograd.Function):
         _call("pcfa_lookup_convc1_bwd", _ptr(st.dpyr), _ptr(c), _ptr(ctx.packed), _ptr(out), _ptr(g), st.B, st.H, st.W,
               st.L, st.r, ctx.cout, ctx.relu)
         return _token_grad(st, g.device), None, None, None, None, None
+
+
+# --------------------------------------------------------------------------- #
+# RAFT motion encoder with ONE backward for all refinement iterations (Config.motion_bwd = "batched")
+# --------------------------------------------------------------------------- #
+class _MotionState:
+    """Slabs [iters, C, H, W] and bookkeeping shared by the flush node and its step nodes."""
+    __slots__ = ("iters", "H", "W", "corr", "w", "cor1", "cf", "rest", "d_rest", "coords", "arrived", "token_grad", "packs")
+
+
+def _slab_image(slab, i):
+    """Image i of a slab [n, C, H, W] as a tensor of its own on the same storage -- NOT a view: autograd tracks in-place
+    writes per base tensor, and a later iteration's forward writing ITS image would otherwise invalidate the images that
+    earlier nodes saved for their backward."""
+    n = slab[0].numel()
+    return torch.empty(0, device=slab.device, dtype=slab.dtype).set_(
+        slab.untyped_storage(), slab.storage_offset() + i * n, (1,) + tuple(slab.shape[1:]))
+
+
+class _MotionFlush(torch.autograd.Function):
+    """corr token -> alias of it that every step node consumes, so this node's backward runs after ALL of them and before
+    _CorrBuild's (the idiom of _CorrBuild / gru._Fanout).  The coordinates and the flow are detached every iteration
+    (models/raft/raft.py:122-123), so the motion encoder's backward feeds nothing but the pyramid gradient, which is
+    consumed once, after the last iteration's backward: the two 3x3 data gradients (conv, convc2) of all iterations run here
+    as one launch each over the slabs (pcfa_conv3x3_run_strided, batch = iters) instead of one small-grid launch per
+    iteration, followed by the per-iteration pcfa_lookup_convc1_bwd launches in the order autograd ran them in (last
+    iteration first): every sum is formed as before, bit for bit."""
+
+    @staticmethod
+    def forward(ctx, token, ms):
+        ctx.ms = ms
+        return token.view_as(token)
+
+    @staticmethod
+    def backward(ctx, grad_token):
+        ms = ctx.ms
+        st = ms.corr
+        live = [i for i in range(ms.iters) if ms.arrived[i]]
+        ms.arrived = [False] * ms.iters
+        ms.token_grad = None
+        if not live:
+            return None, None
+        H, W, plane = ms.H, ms.W, ms.H * ms.W
+        (bwd_c, k_c, n_c), (bwd_c2, k_c2, n_c2) = ms.packs   # conv: cf (k_c) -> n_c ; convc2: cor1 (k_c2) -> n_c2 (< k_c)
+        dev = ms.rest.device
+        wr = ms.rest.shape[1]
+        lib = _hip.load()
+        n = ms.iters
+        # one launch for all iterations only where it forms every sum as the per-iteration launches do: the direct
+        # F(2x2,3x3) kernel both for the batch and for the single-image shapes those launches have (small maps run K slices
+        # or F(4x4,3x3) at batch 1: another order of summation) -- pcfa_conv3x3_run_strided refuses the same cases
+        direct = lambda b, k, n_: (lib.pcfa_conv3x3_algo(b, k, n_, H, W) == 23   # noqa: E731
+                                   and lib.pcfa_conv3x3_workspace_bytes(b, k, n_, H, W) == 0)
+        batched = (len(live) == n and all(direct(b, k, n_) for b in (1, n)
+                                          for k, n_ in ((n_c, k_c), (n_c, n_c2), (n_c2, k_c2))))
+        d_cor1 = torch.empty((n, k_c2, H, W), device=dev, dtype=torch.float32)
+        if batched:
+            # d cf: only the n_c2 channels convc2 produced are live (the convf2 channels feed the detached flow's branch)
+            d_cf = torch.empty((n, n_c2, H, W), device=dev, dtype=torch.float32)
+            _call("pcfa_conv3x3_run_strided", _ptr(ms.d_rest), wr * plane, _ptr(bwd_c), None, _ptr(ms.cf), k_c * plane, None, 0,
+                  _ptr(d_cf), n_c2 * plane, n, n_c, n_c2, H, W, 0, 0., 0, None, ctypes.c_size_t(0))
+            _call("pcfa_conv3x3_run_strided", _ptr(d_cf), n_c2 * plane, _ptr(bwd_c2), None, _ptr(ms.cor1), k_c2 * plane, None, 0,
+                  _ptr(d_cor1), k_c2 * plane, n, n_c2, k_c2, H, W, 0, 0., 0, None, ctypes.c_size_t(0))
+        if st.dpyr is None:
+            st.dpyr = torch.zeros_like(st.pyr)
+            st.coords_bwd = []
+        packed = _convc1_packed(ms.w["convc1"][0])
+        for i in reversed(live):
+            if not batched:   # the per-iteration launches of conv3x3_cat's backward
+                d_cf = torch.empty((1, k_c, H, W), device=dev, dtype=torch.float32)
+                _conv3x3_run(dev, _ptr_off(ms.d_rest, i * wr * plane), bwd_c, None, _ptr_off(ms.cf, i * k_c * plane), None,
+                             _ptr(d_cf), 1, n_c, k_c, H, W)
+                _conv3x3_run(dev, _ptr(d_cf), bwd_c2, None, _ptr_off(ms.cor1, i * k_c2 * plane), None,
+                             _ptr_off(d_cor1, i * k_c2 * plane), 1, n_c2, k_c2, H, W)
+            st.coords_bwd.append(ms.coords[i])
+            _call("pcfa_lookup_convc1_bwd", _ptr(st.dpyr), _ptr(ms.coords[i]), _ptr(packed), _ptr_off(ms.cor1, i * k_c2 * plane),
+                  _ptr_off(d_cor1, i * k_c2 * plane), st.B, st.H, st.W, st.L, st.r, k_c2, 1)
+        return grad_token, None
+
+
+class _MotionStep(torch.autograd.Function):
+    """Iteration i of the motion encoder (models/raft/update.py:79-101) as one node: token, coords, flow -> motion features,
+    written into slab i by the launches the layer-by-layer path issues (fused lookup + convc1, convf1, convc2 | convf2 as a
+    pair, conv, the flow tail).  Its backward launches nothing: it notes that the gradient of slab i has arrived (_GruStep
+    writes it in place: gru_step(d_rest_dst=...)) and leaves the work to _MotionFlush."""
+
+    @staticmethod
+    def forward(ctx, token, coords, flow, ms, i):
+        st = ms.corr
+        c = coords.contiguous()
+        (wc1, bc1), (wc2, bc2), (wf1, bf1), (wf2, bf2), (wc, bc) = (ms.w[k] for k in ("convc1", "convc2", "convf1", "convf2", "conv"))
+        cor1, cf, rest = _slab_image(ms.cor1, i), _slab_image(ms.cf, i), _slab_image(ms.rest, i)
+        _call("pcfa_lookup_convc1_fwd", _ptr(st.pyr), _ptr(c), _ptr(_convc1_packed(wc1)), _ptr(bc1), _ptr(cor1), st.B, st.H,
+              st.W, st.L, st.r, wc1.shape[0], 1)
+        flo1 = conv_fewin(flow, wf1, bf1, True)
+        _conv3x3_cat_fill([cor1, flo1.contiguous()], [wc2, wf2], [bc2, bf2], (), cf)
+        _conv3x3_cat_fill([cf], [wc], [bc], (flow,), rest)
+        ms.coords[i] = c
+        ctx.ms, ctx.i = ms, i
+        ctx.set_materialize_grads(False)
+        return rest
+
+    @staticmethod
+    def backward(ctx, g):
+        ms, i = ctx.ms, ctx.i
+        if g is None:
+            return None, None, None, None, None
+        dst = _slab_image(ms.d_rest, i)
+        if g.data_ptr() != dst.data_ptr() or not g.is_contiguous():   # (the gradient arrived somewhere else)
+            dst.copy_(g)
+        ms.arrived[i] = True
+        tg = None
+        if ms.token_grad is None:   # one (zero) gradient per backward pass orders the flush node behind every step node
+            tg = ms.token_grad = torch.zeros(1, device=g.device, dtype=torch.float32)
+        return tg, None, None, None, None
+
+
+class MotionSteps:
+    """The motion encoder of `iters` refinement iterations with a batched backward; see motion_steps()."""
+
+    def __init__(self, ms, token):
+        self._ms, self._token = ms, token
+
+    def step(self, i, coords, flow):
+        """relu-deferred motion features [1, C, H, W] of iteration i (a slice of the slab)."""
+        _dev(coords, flow)
+        if coords.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError("motion_steps: coords.requires_grad is not supported (detach the coordinates, as "
+                               "models/raft/raft.py:122-123 does)")
+        if flow.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError("motion_steps: the flow must be detached (models/raft/raft.py:122-123)")
+        return _MotionStep.apply(self._token, coords, flow, self._ms, i)
+
+    def d_rest_dst(self, i):
+        """Where iteration i's consumer (gru_step) writes the gradient of step(i)'s result."""
+        return _slab_image(self._ms.d_rest, i)
+
+
+def motion_steps(corr_block, iters, convc1, convc2, convf1, convf2, conv):
+    """RAFT's motion encoder for `iters` iterations on one image, each layer given as (frozen weight, bias), with its
+    backward deferred and batched (_MotionFlush).  Contract: every step's ONLY consumer is gru_step(rest_relu_channels = conv's
+    output channels), as with conv3x3_cat(grad_premasked=True, mask_input_grads=True).  Returns None where the fused
+    lookup or the slab layout does not apply (the caller then runs the layers one by one)."""
+    if not isinstance(corr_block, CorrBlock) or iters < 1:
+        return None
+    st = corr_block._state
+    (wc1, bc1), (wc2, bc2), (wf1, bf1), (wf2, bf2), (wc, bc) = convc1, convc2, convf1, convf2, conv
+    if (st.B != 1 or st.L != 4 or st.r != 4 or bc1 is None or tuple(wc1.shape) != (256, 324, 1, 1)
+            or not corr_block._token.requires_grad
+            or any(t is None or t.requires_grad for t in (wc1, bc1, wc2, bc2, wf1, bf1, wf2, bf2, wc, bc))
+            or any(tuple(w.shape[2:]) != (3, 3) for w in (wc2, wf2, wc))
+            or (wf1.shape[1], wf1.shape[2]) not in FEWIN_SHAPES or wf1.shape[2] != wf1.shape[3]
+            or wc2.shape[1] != wc1.shape[0] or wf2.shape[1] != wf1.shape[0] or wc.shape[1] != wc2.shape[0] + wf2.shape[0]):
+        return None
+    dev = st.pyr.device
+    ms = _MotionState()
+    ms.iters, ms.H, ms.W, ms.corr = iters, st.H, st.W, st
+    ms.w = {"convc1": convc1, "convc2": convc2, "convf1": convf1, "convf2": convf2, "conv": conv}
+    new = lambda c: torch.empty((iters, c, st.H, st.W), device=dev, dtype=torch.float32)  # noqa: E731
+    ms.cor1, ms.cf = new(wc1.shape[0]), new(wc.shape[1])
+    ms.rest, ms.d_rest = new(wc.shape[0] + 2), new(wc.shape[0] + 2)
+    ms.coords, ms.arrived, ms.token_grad = [None] * iters, [False] * iters, None
+    # (data-gradient packing, input channels of the gradient, output channels): conv, then convc2
+    ms.packs = ((_conv3x3_packed(wc)[1], wc.shape[1], wc.shape[0]), (_conv3x3_packed(wc2)[1], wc2.shape[1], wc2.shape[0]))
+    return MotionSteps(ms, _MotionFlush.apply(corr_block._token, ms))
 
 
 class CorrBlock:

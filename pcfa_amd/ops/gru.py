@@ -144,7 +144,7 @@ class _GruStep(torch.autograd.Function):
     contribution of the constant context features (bias included)."""
 
     @staticmethod
-    def forward(ctx, h, rest, w_zr1, p_zr1, w_q1, p_q1, w_zr2, p_zr2, w_q2, p_q2, rest_relu_channels=0):
+    def forward(ctx, h, rest, w_zr1, p_zr1, w_q1, p_q1, w_zr2, p_zr2, w_q2, p_q2, rest_relu_channels=0, d_rest_dst=None):
         _dev(h, rest, w_zr1, p_zr1, w_q1, p_q1, w_zr2, p_zr2, w_q2, p_q2)
         h, rest = h.contiguous(), rest.contiguous()
         B, C, H, W = h.shape
@@ -186,6 +186,10 @@ class _GruStep(torch.autograd.Function):
             raise ValueError("gru_step: rest_relu_channels %d outside [0, %d]" % (ctx.rest_relu, Cr))
         ctx.save_for_backward(*saved, *((rest,) if ctx.rest_relu else ()))
         ctx.packs, ctx.dims = packs, (B, C, Cr, H, W)
+        if d_rest_dst is not None and (tuple(d_rest_dst.shape) != tuple(rest.shape) or not d_rest_dst.is_contiguous()
+                                       or d_rest_dst.dtype != torch.float32 or d_rest_dst.device != rest.device):
+            raise ValueError("gru_step: d_rest_dst must be a contiguous float32 tensor of rest's shape %s" % (tuple(rest.shape),))
+        ctx.d_rest_dst = d_rest_dst   # where the backward writes the gradient of `rest` (None: a fresh tensor)
         return h
 
     @staticmethod
@@ -196,7 +200,7 @@ class _GruStep(torch.autograd.Function):
         n = C * H * W
         new = lambda c: torch.empty((B, c, H, W), device=g.device, dtype=torch.float32)  # noqa: E731
         g = g.contiguous()
-        d_rest = new(Cr)
+        d_rest = new(Cr) if ctx.d_rest_dst is None else ctx.d_rest_dst
         grads_p = [None, None, None, None]  # p_zr1, p_q1, p_zr2, p_q2
         if C % 32 == 0 and _GRU_EPILOGUES:
             # Elementwise backward kernels ride in the epilogues of the data-gradient convolutions: only the update
@@ -219,7 +223,7 @@ class _GruStep(torch.autograd.Function):
             else:
                 _call("pcfa_sepconv5_fwd_split", _ptr(dzr0), 2 * C, None, 0, _ptr(b_zr0), _ptr(dh0), C, 1, _ptr(d_rest), 1,
                       B, C + Cr, H, W, v0)
-            return dh0, d_rest, None, dzr0, None, dqc0, None, dzr1, None, dqc1, None
+            return dh0, d_rest, None, dzr0, None, dqc0, None, dzr1, None, dqc1, None, None
         rest_started = 0
         for half in (1, 0):
             z, r, q, h = ctx.saved_tensors[4 * half: 4 * half + 4]
@@ -244,7 +248,7 @@ class _GruStep(torch.autograd.Function):
                       B, C + Cr, H, W, vertical)
             grads_p[2 * half], grads_p[2 * half + 1] = dzr, dqc
             g = dh
-        return g, d_rest, None, grads_p[0], None, grads_p[1], None, grads_p[2], None, grads_p[3], None
+        return g, d_rest, None, grads_p[0], None, grads_p[1], None, grads_p[2], None, grads_p[3], None, None
 
 
 class _Fanout(torch.autograd.Function):
@@ -337,13 +341,14 @@ def fanout(x, n):
     return _Fanout.apply(x, n) if n > 1 else (x,)
 
 
-def gru_step(h, rest, halves, rest_relu_channels=0):
+def gru_step(h, rest, halves, rest_relu_channels=0, d_rest_dst=None):
     """SepConvGRU update from precomputed context parts: halves = ((w_zr, p_zr, w_q, p_q) for the 1x5 half-step,
     (..) for the 5x1 half-step); see _GruStep.  rest_relu_channels = n > 0: rest[:, :n] are ReLU outputs whose producer
     ran with grad_premasked=True and has no other consumer -- the gradient returned for them is already multiplied
-    by [rest > 0] (applied by the kernel that writes it last)."""
+    by [rest > 0] (applied by the kernel that writes it last).  d_rest_dst: a contiguous tensor of rest's shape that the
+    backward writes the gradient of `rest` into and returns (ops.motion_steps: iteration i's slice of the gradient slab)."""
     (a, b, c, d), (e, f, g_, i_) = halves
-    return _GruStep.apply(h, rest, a, b, c, d, e, f, g_, i_, int(rest_relu_channels))
+    return _GruStep.apply(h, rest, a, b, c, d, e, f, g_, i_, int(rest_relu_channels), d_rest_dst)
 
 
 def sepconv5(a, b, weight):
