@@ -811,7 +811,9 @@ PCFA_API int pcfa_upsample_bilinear_bwd(const float* grad_out, float* grad_in, i
  *   forward : y = relu?((x - mean) * rstd), rstd = 1/sqrt(var + eps)
  *   backward: grad_x = rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = grad_out * (xhat > 0) if relu else grad_out
  * Two launches each {partial sums, apply}; sums are accumulated in fp64 and combined in index order (bitwise
- * reproducible).  pcfa_add_relu_fwd: out = relu(a + b), the block output of ResidualBlock.forward
+ * reproducible).  planes > 65535 returns PCFA_ERR_UNSUPPORTED before any launch (planes is a grid's y extent); null
+ * pointers, planes < 1, plane < 1, eps < 0 or NaN: PCFA_ERR_INVALID_ARG; a workspace that is not 16-B aligned:
+ * PCFA_ERR_WORKSPACE.  pcfa_add_relu_fwd: out = relu(a + b), the block output of ResidualBlock.forward
  * (extractor.py:50-58); its backward for both operands is pcfa_relu_bwd(out, grad_out, ...). */
 PCFA_API size_t pcfa_instnorm_workspace_bytes(int planes, long long plane);
 PCFA_API int pcfa_instnorm_fwd(const float* x, float* y, float* mean_rstd, void* workspace, int planes,

@@ -311,6 +311,7 @@ extern "C" size_t pcfa_instnorm_workspace_bytes(int planes, long long plane) {
 extern "C" int pcfa_instnorm_fwd(const float* x, float* y, float* mean_rstd, void* workspace, int planes,
                                  long long plane, float eps, int relu, void* stream) {
   if (!x || !y || !mean_rstd || !workspace || planes < 1 || plane < 1 || !(eps >= 0.f)) return PCFA_ERR_INVALID_ARG;
+  if (planes > 65535) return PCFA_ERR_UNSUPPORTED;   // the two-launch form puts planes in grid.y
   if (!aligned16(workspace)) return PCFA_ERR_WORKSPACE;
   const NormPlan p = norm_plan(planes, plane);
   const int vec = plane % 4 == 0 && aligned16(x) && aligned16(y);
@@ -340,6 +341,7 @@ extern "C" int pcfa_instnorm_bwd(const float* x, const float* mean_rstd, const f
                                  void* workspace, int planes, long long plane, int relu, void* stream) {
   if (!x || !mean_rstd || !grad_out || !grad_x || !workspace || planes < 1 || plane < 1)
     return PCFA_ERR_INVALID_ARG;
+  if (planes > 65535) return PCFA_ERR_UNSUPPORTED;
   if (!aligned16(workspace)) return PCFA_ERR_WORKSPACE;
   const NormPlan p = norm_plan(planes, plane);
   const int vec = plane % 4 == 0 && aligned16(x) && aligned16(grad_out) && aligned16(grad_x);
