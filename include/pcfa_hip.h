@@ -433,6 +433,25 @@ PCFA_API int pcfa_flow_loss_bwd(const float* pred, const long long pred_strides[
                        const float* grad_loss, float* grad_pred, float* grad_delta1,
                        float* grad_delta2, void* stream);
 
+/* The same loss for `items` INDEPENDENT attacks in one launch per kernel (1 <= items <= PCFA_MAX_ITEMS; 0 or less is
+ * PCFA_ERR_INVALID_ARG, more is PCFA_ERR_UNSUPPORTED).  Item b is pcfa_flow_loss_fwd / _bwd with B = 1 on pred[b], target[b]
+ * (the views' batch strides), delta1 + b*n1, delta2 + b*n2: the items ride on the grid's y axis and each runs the blocks,
+ * threads and summation order of the single call, so every item's scalars and gradients equal the single call's bit for
+ * bit.  out_scalars: [items][8], laid out as above; out_total[0] = ((L_0 + L_1) + ...) in fp32, in item order.
+ * workspace >= items * pcfa_flow_loss_workspace_bytes().  grad_loss is ONE scalar (the gradient of the total), grad_pred is
+ * dense [items][2][H][W], grad_delta1/2 are [items][n1]/[items][n2]; the relu tie rule holds per item.  (Added without a
+ * change of PCFA_ABI_VERSION, like the other additive entry points.) */
+#define PCFA_MAX_ITEMS 16
+PCFA_API int pcfa_flow_loss_items_fwd(const float* pred, const long long pred_strides[4], const float* target,
+                                      const long long target_strides[4], int items, int H, int W, const float* delta1,
+                                      long long n1, const float* delta2, long long n2, float delta_bound, float mu,
+                                      int f_type, float* out_scalars, float* out_total, void* workspace, void* stream);
+PCFA_API int pcfa_flow_loss_items_bwd(const float* pred, const long long pred_strides[4], const float* target,
+                                      const long long target_strides[4], int items, int H, int W, const float* delta1,
+                                      long long n1, const float* delta2, long long n2, float mu, int f_type, int joint,
+                                      const float* fwd_scalars, const float* grad_loss, float* grad_pred,
+                                      float* grad_delta1, float* grad_delta2, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * SepConvGRU gate arithmetic (models/raft/update.py:45-60 == models/gma/update.py:51-66), fused:
  *   gates : z = sigmoid(zc), r = sigmoid(rc), rh = r * h            (zc, rc = convz(hx), convr(hx))
@@ -847,6 +866,12 @@ PCFA_API int pcfa_avg_epe(const float* flow1, const long long strides1[4], const
                  const long long strides2[4], int B, int H, int W, float* out, void* workspace,
                  void* stream);
 PCFA_API int pcfa_sum_squares(const float* x, long long n, float* out, void* workspace, void* stream);
+/* Per-item metrics in one launch pair: out[b] = pcfa_avg_epe of (flow1[b], flow2[b]) with B = 1, resp. pcfa_sum_squares of
+ * x + b*n, bit for bit.  items and workspace as for pcfa_flow_loss_items_fwd. */
+PCFA_API int pcfa_avg_epe_items(const float* flow1, const long long strides1[4], const float* flow2,
+                                const long long strides2[4], int items, int H, int W, float* out, void* workspace,
+                                void* stream);
+PCFA_API int pcfa_sum_squares_items(const float* x, int items, long long n, float* out, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * L-BFGS vector math of the attack loop: the memory update and the two-loop
@@ -890,6 +915,19 @@ PCFA_API int pcfa_lbfgs_gram_update(const float* g, float* g_prev, const float* 
                                     void* state, void* workspace, int capacity, long long ld, void* stream);
 PCFA_API int pcfa_lbfgs_gram_direction(const float* g, const float* S, const float* Y, void* state, float* d,
                                        float* out_gtd_dmax, void* workspace, int capacity, long long ld, void* stream);
+/* The Gram form for `items` independent optimisers (1 <= items <= PCFA_MAX_ITEMS) in the same five kernels, item b on the
+ * grid's y axis with the blocks and summation order of the single call: bit-identical to it item by item.  Every buffer
+ * is the single call's, dense per item: g, g_prev, d [items][ld]; S, Y [items][capacity + 1][ld]; state
+ * [items][pcfa_lbfgs_gram_state_bytes]; workspace [items][pcfa_lbfgs_gram_workspace_bytes]; out_gtd_dmax [items][2].
+ * Bit b of `live` (reset: of `mask`) selects item b; an item whose bit is clear is neither read nor written.  t: `items`
+ * step lengths on the HOST, handed to the kernel by value. */
+PCFA_API int pcfa_lbfgs_gram_reset_items(void* state, int capacity, int items, unsigned mask, void* stream);
+PCFA_API int pcfa_lbfgs_gram_update_items(const float* g, float* g_prev, const float* d, const float* t, float* S,
+                                          float* Y, void* state, void* workspace, int capacity, long long ld, int items,
+                                          unsigned live, void* stream);
+PCFA_API int pcfa_lbfgs_gram_direction_items(const float* g, const float* S, const float* Y, void* state, float* d,
+                                             float* out_gtd_dmax, void* workspace, int capacity, long long ld, int items,
+                                             unsigned live, void* stream);
 
 #ifdef __cplusplus
 }

@@ -201,7 +201,20 @@ SIGNATURES = {
     "pcfa_sum_n": (c_int, [POINTER(c_void_p), c_int, _P, c_longlong, _P]),
     "pcfa_avg_epe": (c_int, [_P, _S4, _P, _S4, c_int, c_int, c_int, _P, _P, _P]),
     "pcfa_sum_squares": (c_int, [_P, c_longlong, _P, _P, _P]),
+    # `items` independent attacks per launch (item b on the grid's y axis, bit-identical to the single calls)
+    "pcfa_flow_loss_items_fwd": (c_int, [_P, _S4, _P, _S4, c_int, c_int, c_int, _P, c_longlong, _P, c_longlong,
+                                         c_float, c_float, c_int, _P, _P, _P, _P]),
+    "pcfa_flow_loss_items_bwd": (c_int, [_P, _S4, _P, _S4, c_int, c_int, c_int, _P, c_longlong, _P, c_longlong,
+                                         c_float, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    "pcfa_avg_epe_items": (c_int, [_P, _S4, _P, _S4, c_int, c_int, c_int, _P, _P, _P]),
+    "pcfa_sum_squares_items": (c_int, [_P, c_int, c_longlong, _P, _P, _P]),
+    "pcfa_lbfgs_gram_reset_items": (c_int, [_P, c_int, c_int, c_uint, _P]),
+    "pcfa_lbfgs_gram_update_items": (c_int, [_P, _P, _P, POINTER(c_float), _P, _P, _P, _P, c_int, c_longlong, c_int,
+                                             c_uint, _P]),
+    "pcfa_lbfgs_gram_direction_items": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_longlong, c_int, c_uint, _P]),
 }
+
+MAX_ITEMS = 16   # PCFA_MAX_ITEMS
 
 _lib = None
 

@@ -27,7 +27,7 @@ import time
 import numpy as np
 import torch
 
-from . import config, ops, sharding
+from . import _hip, config, ops, sharding
 from .helper_functions import datasets, logging, losses, ownutilities, parsing_file, targets
 from .helper_functions.config_paths import Conf
 
@@ -66,6 +66,17 @@ def select_device():
 def _should_save(batch, args):
     return ((batch % args.save_frequency == 0 and not args.small_save) or (args.small_save and batch < 32)) \
         and not args.no_save
+
+
+def best_iterate_rule(below_threshold, l2_delta12, aee_adv_tgt, delta12_min, aee_adv_tgt_min, delta_bound):
+    """The best-iterate rule (attack_PCFA.py:226-243), stated once for PairAttack.step and PairBatch.step: until an iterate
+    has met the bound the smallest perturbation wins (ties: the smaller AEE to the target); from then on the smallest AEE
+    to the target among the iterates inside the bound.  Returns (record this iterate, an iterate has met the bound)."""
+    if below_threshold:
+        return l2_delta12 <= delta_bound and aee_adv_tgt < aee_adv_tgt_min, True
+    if l2_delta12 < delta12_min or (l2_delta12 == delta12_min and aee_adv_tgt < aee_adv_tgt_min):
+        return True, l2_delta12 <= delta_bound
+    return False, False
 
 
 def _graphs_enabled(device, args):
@@ -382,16 +393,9 @@ class PairAttack:
         self.aee_adv_tgt, self.aee_adv_pred = aee_adv_tgt, aee_adv_pred
         self.l2_delta1, self.l2_delta2, self.l2_delta12 = l2_delta1, l2_delta2, l2_delta12
 
-        # best-iterate rule, attack_PCFA.py:226-243
-        update_minima = False
-        if not self.delta_below_threshold:
-            if l2_delta12 < self.delta12_min_val or (l2_delta12 == self.delta12_min_val
-                                                     and aee_adv_tgt < self.aee_adv_tgt_min_val):
-                update_minima = True
-                if l2_delta12 <= args.delta_bound:
-                    self.delta_below_threshold = True
-        elif l2_delta12 <= args.delta_bound and aee_adv_tgt < self.aee_adv_tgt_min_val:
-            update_minima = True
+        update_minima, self.delta_below_threshold = best_iterate_rule(
+            self.delta_below_threshold, l2_delta12, aee_adv_tgt, self.delta12_min_val, self.aee_adv_tgt_min_val,
+            args.delta_bound)
         if update_minima:
             self.delta12_min_val = l2_delta12
             self.aee_adv_tgt_min_val = aee_adv_tgt
@@ -434,6 +438,308 @@ def pcfa_attack(model, image1, image2, flow, batch, distortion_folder, eps_box, 
     if distortion_folder is not None and _should_save(batch, args):
         st.save(distortion_folder)
     return st.result()
+
+
+class _BatchGraphs:
+    """_PairGraphs for a PairBatch: the static buffers, hipGraphs and optimiser of one (shape, flags, B)."""
+
+    def __init__(self, st):
+        self.image1, self.image2 = st.image1, st.image2
+        self.images_max, self.images_min = st.images_max, st.images_min
+        self.params, self.target, self.optimizer = st.params, st.target, st.optimizer
+        self.graphed, self.repredict = st.graphed, st.repredict
+        self.owner = weakref.ref(st)
+
+    retire_owner = _PairGraphs.retire_owner
+
+
+def _batch_graph_cache(model):
+    """Graph sets of PairBatch, a cache of their own next to PCFA's pair cache (whose cap they do not count against)."""
+    cache = getattr(model, "_pcfa_pair_batch_graphs", None)
+    if cache is None:
+        cache = {}
+        try:
+            object.__setattr__(model, "_pcfa_pair_batch_graphs", cache)
+        except Exception:  # noqa: BLE001
+            return {}
+    return cache
+
+
+class _ItemRecord:
+    """What PairAttack keeps per pair besides the variables: the constant metrics, the last step's metrics, the best
+    iterate."""
+
+    def __init__(self, batch):
+        self.batch = batch
+        self.aee_gt = self.aee_tgt = self.aee_gt_tgt = None
+        self.delta_below_threshold = False
+        self.delta12_min_val = float('inf')
+        self.aee_adv_tgt_min_val = float('inf')
+        self.aee_adv_pred_min_val = 0.
+        self.delta1_min = self.delta2_min = self.flow_pred_min = None
+        self.aee_adv_gt = 0.
+        self.aee_adv_tgt = self.aee_adv_pred = 0.
+        self.l2_delta1 = self.l2_delta2 = self.l2_delta12 = 0.
+
+
+class PairBatch:
+    """B independent PairAttacks whose closure evaluations are ONE forward and backward at batch B, on one stream, in one
+    graph: per item its own variables, target (from its own unattacked flow), L-BFGS state (lbfgs.BatchedLBFGS) and
+    best-iterate record.  Pair b's variables enter only pair b's loss term, so the gradient of the summed loss with respect
+    to them is exactly that pair's own gradient (ops.loss_delta_constraint_items); what differs from attacking the pair
+    alone is the rounding of the network's kernels at batch B (and, under the fixed-point scatters, a shift shared by the
+    batch).  With B = 1 every bit equals PairAttack's.
+
+    pairs: B x (batch, image1 [1,3,H,W], image2, flow or None), all of one shape.  `step()` = BatchedLBFGS.step, one
+    re-prediction at batch B, the per-item metrics from one launch each and one read-back.  Item b's metrics are logged
+    under its own `batch * steps + step`; `result(b)` is its 12-tuple, `save(folder, b)` writes its artefacts.  Capture as
+    in PairAttack (eager fallback with a warning); the graph sets live in a cache of their own on the model, keyed by
+    PairAttack's key + (B,), LRU with Config.max_cached_shapes entries."""
+
+    def __init__(self, model, pairs, eps_box, device, has_gt, optim_mu, args, use_graph=None):
+        self.model, self.args, self.device = model, args, device
+        self.has_gt, self.optim_mu, self.eps_box = has_gt, optim_mu, eps_box
+        self.items = B = len(pairs)
+        self.rec = [_ItemRecord(batch) for batch, _, _, _ in pairs]
+        shapes = {tuple(p[1].shape) for p in pairs} | {tuple(p[2].shape) for p in pairs}
+        if len(shapes) != 1 or next(iter(shapes))[0] != 1:
+            raise ValueError("PairBatch: every pair is two [1,3,H,W] images of one shape, got %s" % sorted(shapes))
+        image1 = torch.cat([p[1] for p in pairs]).to(device)
+        image2 = torch.cat([p[2] for p in pairs]).to(device)
+        self.flow_gt = torch.cat([p[3] for p in pairs]).to(device) if has_gt else None
+        if not ownutilities.model_takes_unit_input(args.net):
+            image1 = image1 / 255.
+            image2 = image2 / 255.
+        self.padder, [image1, image2] = ownutilities.preprocess_img(args.net, image1, image2)
+        cov = args.boxconstraint in ['change_of_variables']
+        joint = bool(args.joint_perturbation)
+        if joint and cov:
+            raise ValueError("Training a --joint_perturbation with --boxconstraint=change_of_variables is not "
+                             "defined. Please use --boxconstraint=clipping.")
+        if use_graph is None:
+            use_graph = _graphs_enabled(device, args)
+        self.graph_key = (args.net, (1,) + tuple(image1.shape[1:]), args.boxconstraint, joint, args.loss, float(optim_mu),
+                          float(args.delta_bound), float(eps_box), str(device), ops.core.current_lane(), B)
+        cache = _batch_graph_cache(model)
+        kept = cache.get(self.graph_key) if (use_graph and config.cfg(model).reuse_pair_graphs) else None
+        self.graphs_reused = kept is not None
+        self.retired = False
+        if kept is not None:
+            kept.retire_owner()
+            kept.owner = weakref.ref(self)
+            self._cache_put(kept)
+            self.image1, self.image2 = kept.image1, kept.image2
+            self.images_max, self.images_min = kept.images_max, kept.images_min
+            self.params, self.target, self.optimizer = kept.params, kept.target, kept.optimizer
+            self.graphed, self.repredict = kept.graphed, kept.repredict
+            self.optimizer.reset()
+        else:
+            self.image1, self.image2 = torch.empty_like(image1), torch.empty_like(image2)
+            self.images_max, self.images_min = torch.empty_like(image1), torch.empty_like(image1)
+            self.params = [torch.zeros_like(image1).requires_grad_() for _ in range(1 if joint else 2)]
+            self.target = None
+            self.optimizer = ops.get().BatchedLBFGS(self.params, items=B, max_iter=10)
+            self.graphed = self.repredict = None
+        with torch.no_grad():
+            self.image1.copy_(image1)
+            self.image2.copy_(image2)
+            self.images_max.copy_(torch.max(image1, image2))
+            self.images_min.copy_(torch.min(image1, image2))
+            if joint:
+                self.params[0].zero_()
+            elif cov:
+                self.params[0].copy_(torch.atanh(2. * (1. - eps_box) * image1 - (1 - eps_box)))
+                self.params[1].copy_(torch.atanh(2. * (1. - eps_box) * image2 - (1 - eps_box)))
+            else:
+                self.params[0].copy_(image1)
+                self.params[1].copy_(image2)
+        for p_ in self.params:
+            p_.grad = None
+        if joint:
+            self.nw_delta = self.params[0]
+            self.nw_input1, self.nw_input2 = self.image1, self.image2
+            self.fwd_kwargs = {"delta1": self.nw_delta}
+        else:
+            self.nw_delta = None
+            self.nw_input1, self.nw_input2 = self.params
+            self.fwd_kwargs = {}
+
+        # the unattacked flow of every item (the forward at the initial variables) and, from it, the item's own target
+        if self.repredict is not None:
+            _, flow0 = self.repredict()
+        else:
+            with torch.no_grad():
+                flow0 = self.predict()
+        self.flow_pred_init = flow0.detach().clone()
+        target = torch.cat([targets.get_target(args.target, self.flow_pred_init[b:b + 1],
+                                               custom_target_path=args.custom_target_path, device=device).to(device)
+                            for b in range(B)])
+        if self.target is None:
+            self.target = target.clone()
+        else:
+            self.target.copy_(target)
+        if kept is not None:
+            kept.target = self.target
+        self.target.requires_grad = False
+
+        om = ops.get()
+        const = [om.avg_epe_items(self.target, self.flow_pred_init)]
+        if has_gt:
+            const += [om.avg_epe_items(self.target, self.flow_gt), om.avg_epe_items(self.flow_pred_init, self.flow_gt)]
+        const = torch.stack(const).tolist()
+        for b, r in enumerate(self.rec):
+            r.aee_tgt = const[0][b]
+            if has_gt:
+                r.aee_gt_tgt, r.aee_gt = const[1][b], const[2][b]
+            curr_step = r.batch * args.steps
+            logging.log_metrics(curr_step, ("aee_pred-tgt", r.aee_tgt), ("aee_gt-tgt", r.aee_gt_tgt),
+                                ("aee_pred-gt", r.aee_gt))
+            logging.log_metric(key="optim_mu", value=optim_mu, step=curr_step)
+        model.zero_grad()
+
+        self.flow_pred = self.flow_pred_init
+        self.delta1, self.delta2 = torch.zeros_like(self.image1), torch.zeros_like(self.image2)
+        self.steps_done = 0
+        self.closures = 0          # evaluations of the batched closure (each one is a closure evaluation of every item)
+        if use_graph and kept is None:
+            self.enable_graph()
+
+    def _cache_put(self, kept):
+        cache, cap = _batch_graph_cache(self.model), _max_cached_shapes(self.model)
+        cache.pop(self.graph_key, None)
+        cache[self.graph_key] = kept             # most recently used last
+        while len(cache) > cap:
+            old_key = next(iter(cache))
+            old = cache.pop(old_key)
+            _log_eviction("pair-batch-graph", old_key)
+            old.retire_owner()
+            old.graphed = old.repredict = old.optimizer = None
+
+    predict = PairAttack.predict
+    current_deltas = PairAttack.current_deltas
+    _repredict_body = PairAttack._repredict_body
+    _retire = PairAttack._retire
+
+    def _check_live(self):
+        if self.retired:
+            raise RuntimeError("this PairBatch was retired: a later batch of the same shape adopted its static buffers, "
+                               "graphs and optimiser")
+
+    def closure_body(self):
+        """Forward at batch B, the per-item losses, ONE backward of their sum; returns the B losses."""
+        flow = self.predict()
+        d1, d2 = self.current_deltas()
+        total, item_losses = ops.get().loss_delta_constraint_items(flow, self.target, d1, d2,
+                                                                   delta_bound=self.args.delta_bound, mu=self.optim_mu,
+                                                                   f_type=self.args.loss)
+        total.backward()
+        return item_losses
+
+    def enable_graph(self):
+        try:
+            from .graphed import GraphedClosure, GraphedForward
+            self.graphed = GraphedClosure(self.closure_body, self.params, grad_sink=self.optimizer.flat_grad_views())
+            self.repredict = GraphedForward(self._repredict_body, self.device)
+            if config.cfg(self.model).reuse_pair_graphs:
+                self._cache_put(_BatchGraphs(self))
+        except Exception as e:  # noqa: BLE001 -- the eager closure launches the same kernels in the same order
+            import logging as pylog
+            pylog.warning("hipGraph capture of the batched closure failed (%r): launching eagerly", e)
+            self.graphed = self.repredict = None
+
+    def closure(self):
+        self._check_live()
+        self.closures += 1
+        if self.graphed is not None:
+            return self.graphed()
+        for p_ in self.params:
+            p_.grad = None
+        return self.closure_body()
+
+    def step(self):
+        """One `--steps` iteration for every item; returns B x (aee_adv_tgt, aee_adv_pred, l2_delta12)."""
+        self._check_live()
+        args, om = self.args, ops.get()
+        steps = self.steps_done
+        for r in self.rec:
+            logging.log_metrics(r.batch * args.steps + steps, ("batch", r.batch), ("steps", steps), ("epoch", 0))
+
+        self.optimizer.step(self.closure)
+
+        if self.repredict is not None:
+            (delta1, delta2), flow_pred = self.repredict()
+        else:
+            with torch.no_grad():
+                (delta1, delta2), flow_pred = self._repredict_body()
+        self.delta1, self.delta2, self.flow_pred = delta1, delta2, flow_pred
+
+        # the metrics of PairAttack.step per item (logging.calc_metrics_adv, calc_delta_metrics: the same fp32 operations
+        # on B values at once), one read-back for all of them
+        n1, n2 = delta1[0].numel(), delta2[0].numel()
+        ss1 = om.sum_squares_items(delta1)
+        ss2 = ss1 if delta2 is delta1 else om.sum_squares_items(delta2)
+        rows = [om.avg_epe_items(flow_pred, self.target), om.avg_epe_items(flow_pred, self.flow_pred_init),
+                torch.sqrt(ss1) / (n1 ** 0.5), torch.sqrt(ss2) / (n2 ** 0.5), torch.sqrt(ss1 + ss2) / ((n1 + n2) ** 0.5)]
+        if self.has_gt:
+            rows.append(om.avg_epe_items(flow_pred, self.flow_gt))
+        rows = torch.stack(rows).tolist()
+        out = []
+        for b, r in enumerate(self.rec):
+            curr_step = r.batch * args.steps + steps
+            r.aee_adv_tgt, r.aee_adv_pred, r.l2_delta1, r.l2_delta2, r.l2_delta12 = (row[b] for row in rows[:5])
+            r.aee_adv_gt = rows[5][b] if self.has_gt else None
+            logging.log_metrics(curr_step, ("aee_predadv-tgt", r.aee_adv_tgt), ("aee_pred-predadv", r.aee_adv_pred),
+                                ("aee_predadv-gt", r.aee_adv_gt))
+            logging.log_metrics(curr_step, ("l2_delta1", r.l2_delta1), ("l2_delta2", r.l2_delta2),
+                                ("l2_delta-avg", r.l2_delta12))
+            update_minima, r.delta_below_threshold = best_iterate_rule(
+                r.delta_below_threshold, r.l2_delta12, r.aee_adv_tgt, r.delta12_min_val, r.aee_adv_tgt_min_val,
+                args.delta_bound)
+            if update_minima:
+                r.delta12_min_val = r.l2_delta12
+                r.aee_adv_tgt_min_val = r.aee_adv_tgt
+                r.aee_adv_pred_min_val = r.aee_adv_pred
+                r.delta1_min = delta1[b:b + 1].detach().clone()
+                r.delta2_min = delta2[b:b + 1].detach().clone()
+                r.flow_pred_min = flow_pred[b:b + 1].detach().clone()
+            logging.log_metrics(curr_step, ("aee_pred-tgt_min", r.aee_adv_tgt_min_val),
+                                ("l2_delta-avg_min", r.delta12_min_val),
+                                ("aee_pred-predadv_min", r.aee_adv_pred_min_val))
+            out.append((r.aee_adv_tgt, r.aee_adv_pred, r.l2_delta12))
+        self.steps_done += 1
+        return out
+
+    def save(self, distortion_folder, b):
+        r, s = self.rec[b], slice(b, b + 1)
+        for tens, name in ((self.delta1[s], "delta1_final"), (self.delta2[s], "delta2_final"),
+                           (r.delta1_min, "delta1_best"), (r.delta2_min, "delta2_best"),
+                           (self.image1[s], "image1"), (self.image2[s], "image2"), (self.target[s], "target"),
+                           (self.flow_pred[s], "flow_pred_final"), (r.flow_pred_min, "flow_pred_best"),
+                           (self.flow_pred_init[s], "flow_pred_init")):
+            logging.save_tensor(tens, name, r.batch, distortion_folder)
+        if self.has_gt:
+            logging.save_tensor(self.flow_gt[s], "flow_gt", r.batch, distortion_folder)
+
+    def result(self, b):
+        """Item b's 12-tuple, as PairAttack.result."""
+        r = self.rec[b]
+        return (r.aee_gt, r.aee_tgt, r.aee_gt_tgt, r.aee_adv_gt, r.aee_adv_tgt, r.aee_adv_pred, r.l2_delta1, r.l2_delta2,
+                r.l2_delta12, r.aee_adv_tgt_min_val, r.aee_adv_pred_min_val, r.delta12_min_val)
+
+
+def group_pairs(stream, per_closure, shape_of):
+    """Collect a stream of pairs, in arrival order, into groups of equal `shape_of(pair)` with up to `per_closure` members:
+    yields a group as soon as it is full and the incomplete ones, oldest first, at the end.  (attack_l2 groups by the
+    image shape: the members of a PairBatch share one padder, so equal padded shapes alone would not do.)"""
+    open_groups = {}
+    for pair in stream:
+        key = shape_of(pair)
+        group = open_groups.setdefault(key, [])
+        group.append(pair)
+        if len(group) == per_closure:
+            yield open_groups.pop(key)
+    for group in open_groups.values():
+        yield group
 
 
 def _load_model(args, device, variable_change):
@@ -578,6 +884,14 @@ def attack_l2(args, data_loader=None, has_gt=None):
     nflight = max(1, int(getattr(args, "pairs_in_flight", 1)))
     if nflight > 1 and torch.device(device).type != "cuda":
         raise ValueError("--pairs_in_flight needs a GPU (lanes are HIP streams)")
+    per_closure = max(1, int(getattr(args, "pairs_per_closure", 1)))
+    if per_closure > 1 and nflight > 1:
+        raise ValueError("--pairs_per_closure and --pairs_in_flight are two ways to put several pairs on one GPU: "
+                         "use one of them")
+    if per_closure > 1 and torch.device(device).type != "cuda":
+        raise ValueError("--pairs_per_closure needs a GPU (the batched optimiser has no CPU path)")
+    if per_closure > _hip.MAX_ITEMS:
+        raise ValueError("--pairs_per_closure: at most %d pairs per closure" % _hip.MAX_ITEMS)
     pending = []   # (batch, image1, image2, flow) of this rank, attacked `nflight` at a time
 
     def attack_group(group):
@@ -600,15 +914,32 @@ def attack_l2(args, data_loader=None, has_gt=None):
                 st.save(distortion_folder)
             local.append((batch,) + tuple(float('nan') if v is None else float(v) for v in st.result()))
 
-    for batch, (image1, image2, flow, _) in enumerate(data_loader):
-        if batch % world != rank:
-            continue
-        pending.append((batch, image1, image2, flow))
-        if len(pending) == nflight:
+    def attack_batch(group):
+        # one closure for the whole group (PairBatch): every pair keeps its own variables, target, optimiser state and
+        # best-iterate record, and its row goes out under its own index
+        if len(group) == 1:
+            return attack_group(group)
+        pb = PairBatch(model, group, EPS_BOX, device, has_gt, optim_mu, args)
+        for _ in range(args.steps):
+            pb.step()
+        for b, (batch, _, _, _) in enumerate(group):
+            if distortion_folder is not None and _should_save(batch, args):
+                pb.save(distortion_folder, b)
+            local.append((batch,) + tuple(float('nan') if v is None else float(v) for v in pb.result(b)))
+
+    mine = ((batch, image1, image2, flow) for batch, (image1, image2, flow, _) in enumerate(data_loader)
+            if batch % world == rank)
+    if per_closure > 1:
+        for group in group_pairs(mine, per_closure, lambda pair: tuple(pair[1].shape)):
+            attack_batch(group)
+    else:
+        for pair in mine:
+            pending.append(pair)
+            if len(pending) == nflight:
+                attack_group(pending)
+                pending = []
+        if pending:
             attack_group(pending)
-            pending = []
-    if pending:
-        attack_group(pending)
 
     rows = sharding.gather_rows(local, width=13, device=device)
     if rank != 0:

@@ -161,18 +161,29 @@ struct View4 {
   long long sb, sc, sh, sw;
 };
 
+// The *_items entry points put item b = blockIdx.y of a batch of independent attacks on the grid's y axis: every base
+// pointer moves by its item stride (in floats) and the item then runs the very blocks, threads and summation order of the
+// single call on its slice -- which is a launch with gridDim.y == 1 and all strides unused.
+struct LossItemStride {
+  long long pred, target, d1, d2;
+};
+
 // partial[block][0]=sum epe, [1]=sum sq diff, [2]=p.t, [3]=p.p, [4]=t.t, [5]=sum d1^2, [6]=sum d2^2
 __global__ __launch_bounds__(RED_THREADS) void loss_partial_kernel(
     const float* __restrict__ pred, View4 ps, const float* __restrict__ target, View4 ts, int B,
     int H, int W, const float* __restrict__ d1, long long n1, const float* __restrict__ d2,
-    long long n2, float* __restrict__ partial) {
+    long long n2, float* __restrict__ partial, LossItemStride is) {
   __shared__ float smem[NSUM * 4];
   float v[NSUM];
 #pragma unroll
   for (int k = 0; k < NSUM; ++k) v[k] = 0.f;
   const long long stride = (long long)gridDim.x * blockDim.x;
   const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long item = blockIdx.y;
+  partial += item * gridDim.x * NSUM;
   if (pred) {
+    pred += item * is.pred;
+    target += item * is.target;
     const long long npix = (long long)B * H * W;
     for (long long i = gid; i < npix; i += stride) {
       const int x = i % W;
@@ -192,10 +203,14 @@ __global__ __launch_bounds__(RED_THREADS) void loss_partial_kernel(
       v[4] += tu * tu + tv * tv;
     }
   }
-  if (d1)
+  if (d1) {
+    d1 += item * is.d1;
     for (long long i = gid; i < n1; i += stride) v[5] += d1[i] * d1[i];
-  if (d2)
+  }
+  if (d2) {
+    d2 += item * is.d2;
     for (long long i = gid; i < n2; i += stride) v[6] += d2[i] * d2[i];
+  }
   block_sum<NSUM>(v, smem);
   if (threadIdx.x == 0) {
 #pragma unroll
@@ -204,13 +219,16 @@ __global__ __launch_bounds__(RED_THREADS) void loss_partial_kernel(
 }
 
 // mode 0: loss_delta_constraint scalars; mode 1: avg_epe only; mode 2: sum of squares (slot 5).
+// Item blockIdx.y reads its own partials and writes out[item * out_stride ...].
 __global__ __launch_bounds__(RED_THREADS) void loss_final_kernel(
     const float* __restrict__ partial, int nblocks, float* __restrict__ out, int mode,
-    float npix, float nelem_flow, float ndelta, float bound_sq, float mu, int f_type) {
+    float npix, float nelem_flow, float ndelta, float bound_sq, float mu, int f_type, int out_stride) {
   __shared__ float smem[NSUM * 4];
   float v[NSUM];
 #pragma unroll
   for (int k = 0; k < NSUM; ++k) v[k] = 0.f;
+  partial += (size_t)blockIdx.y * nblocks * NSUM;
+  out += (size_t)blockIdx.y * out_stride;
   for (int i = threadIdx.x; i < nblocks; i += blockDim.x) {
 #pragma unroll
     for (int k = 0; k < NSUM; ++k) v[k] += partial[(size_t)i * NSUM + k];
@@ -243,12 +261,25 @@ __global__ __launch_bounds__(RED_THREADS) void loss_final_kernel(
   out[6] = msq - bound_sq;
 }
 
+// total = ((L_0 + L_1) + ...) + L_{items-1}: the in-order fp32 sum of the items' losses
+__global__ void loss_items_total_kernel(const float* __restrict__ scal, int items, float* __restrict__ total) {
+  float s = scal[0];
+  for (int b = 1; b < items; ++b) s += scal[(size_t)b * 8];
+  total[0] = s;
+}
+
 __global__ void loss_bwd_flow_kernel(const float* __restrict__ pred, View4 ps,
                                      const float* __restrict__ target, View4 ts, int B, int H,
                                      int W, int f_type, const float* __restrict__ fwd,
-                                     const float* __restrict__ gloss, float* __restrict__ gpred) {
+                                     const float* __restrict__ gloss, float* __restrict__ gpred,
+                                     LossItemStride is) {
   const long long npix = (long long)B * H * W;
   const long long stride = (long long)gridDim.x * blockDim.x;
+  const long long item = blockIdx.y;
+  pred += item * is.pred;
+  target += item * is.target;
+  fwd += item * 8;
+  gpred += item * 2 * npix;
   const float gl = gloss[0];
   const float pt = fwd[3], pp = fwd[4], tt = fwd[5];
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += stride) {
@@ -288,8 +319,12 @@ __global__ void loss_bwd_flow_kernel(const float* __restrict__ pred, View4 ps,
 
 __global__ void loss_bwd_delta_kernel(const float* __restrict__ d, long long n, float ndelta,
                                       float mu, float mult, const float* __restrict__ fwd,
-                                      const float* __restrict__ gloss, float* __restrict__ gd) {
+                                      const float* __restrict__ gloss, float* __restrict__ gd,
+                                      long long item_stride) {
   const long long stride = (long long)gridDim.x * blockDim.x;
+  d += blockIdx.y * item_stride;
+  gd += blockIdx.y * item_stride;
+  fwd += blockIdx.y * 8;
   const float arg = fwd[6];  // msq - bound^2
   // torch.max(0, x) backward: full gradient for x > 0, half at the tie, none below
   const float sel = arg > 0.f ? 1.f : (arg == 0.f ? 0.5f : 0.f);
@@ -564,12 +599,12 @@ extern "C" int pcfa_flow_loss_fwd(const float* pred, const long long pred_stride
   float* partial = (float*)workspace;
   pcfa_launch(loss_partial_kernel, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, s, pred,
                      mkview(pred_strides), target, mkview(target_strides), B, H, W, delta1, n1,
-                     delta2, n2, partial);
+                     delta2, n2, partial, LossItemStride{0, 0, 0, 0});
   PCFA_LAUNCH_CHECK();
   const float bound_sq = (float)((double)delta_bound * (double)delta_bound);
   pcfa_launch(loss_final_kernel, dim3(1), dim3(RED_THREADS), 0, s, partial, RED_BLOCKS,
                      out_scalars, 0, (float)((long long)B * H * W),
-                     (float)((long long)B * 2 * H * W), (float)(n1 + n2), bound_sq, mu, f_type);
+                     (float)((long long)B * 2 * H * W), (float)(n1 + n2), bound_sq, mu, f_type, 0);
   PCFA_LAUNCH_CHECK();
   return PCFA_OK;
 }
@@ -588,20 +623,88 @@ extern "C" int pcfa_flow_loss_bwd(const float* pred, const long long pred_stride
   if (grad_pred) {
     pcfa_launch(loss_bwd_flow_kernel, dim3(ew_blocks((long long)B * H * W)), dim3(256), 0,
                        s, pred, mkview(pred_strides), target, mkview(target_strides), B, H, W,
-                       f_type, fwd_scalars, grad_loss, grad_pred);
+                       f_type, fwd_scalars, grad_loss, grad_pred, LossItemStride{0, 0, 0, 0});
     PCFA_LAUNCH_CHECK();
   }
   const float ndelta = (float)(n1 + n2);
   if (grad_delta1) {
     if (!delta1) return PCFA_ERR_INVALID_ARG;
     pcfa_launch(loss_bwd_delta_kernel, dim3(ew_blocks(n1)), dim3(256), 0, s, delta1, n1,
-                       ndelta, mu, joint ? 2.f : 1.f, fwd_scalars, grad_loss, grad_delta1);
+                       ndelta, mu, joint ? 2.f : 1.f, fwd_scalars, grad_loss, grad_delta1, 0LL);
     PCFA_LAUNCH_CHECK();
   }
   if (grad_delta2) {
     if (!delta2) return PCFA_ERR_INVALID_ARG;
     pcfa_launch(loss_bwd_delta_kernel, dim3(ew_blocks(n2)), dim3(256), 0, s, delta2, n2,
-                       ndelta, mu, 1.f, fwd_scalars, grad_loss, grad_delta2);
+                       ndelta, mu, 1.f, fwd_scalars, grad_loss, grad_delta2, 0LL);
+    PCFA_LAUNCH_CHECK();
+  }
+  return PCFA_OK;
+}
+
+// ---------------------------------------------------------------- B independent attacks in one launch each
+// Item b is the single call above with B = 1 on pred[b], target[b], delta1[b], delta2[b]: same grid x, same blocks, same
+// order, hence the same bits.  delta1 / delta2 are dense [items][n1] / [items][n2]; a joint perturbation passes the same
+// pointer twice.
+namespace {
+inline int items_status(int items) {
+  if (items < 1) return PCFA_ERR_INVALID_ARG;
+  if (items > PCFA_MAX_ITEMS) return PCFA_ERR_UNSUPPORTED;
+  return PCFA_OK;
+}
+}  // namespace
+
+extern "C" int pcfa_flow_loss_items_fwd(const float* pred, const long long pred_strides[4], const float* target,
+                                        const long long target_strides[4], int items, int H, int W, const float* delta1,
+                                        long long n1, const float* delta2, long long n2, float delta_bound, float mu,
+                                        int f_type, float* out_scalars, float* out_total, void* workspace, void* stream) {
+  if (!pred || !target || !pred_strides || !target_strides || !delta1 || !delta2 || !out_scalars || !out_total ||
+      !workspace || H < 1 || W < 1 || n1 < 1 || n2 < 1 || f_type < 0 || f_type > 2)
+    return PCFA_ERR_INVALID_ARG;
+  if (int st = items_status(items)) return st;
+  hipStream_t s = (hipStream_t)stream;
+  float* partial = (float*)workspace;
+  const LossItemStride is{pred_strides[0], target_strides[0], n1, n2};
+  pcfa_launch(loss_partial_kernel, dim3(RED_BLOCKS, items), dim3(RED_THREADS), 0, s, pred, mkview(pred_strides), target,
+              mkview(target_strides), 1, H, W, delta1, n1, delta2, n2, partial, is);
+  PCFA_LAUNCH_CHECK();
+  const float bound_sq = (float)((double)delta_bound * (double)delta_bound);
+  pcfa_launch(loss_final_kernel, dim3(1, items), dim3(RED_THREADS), 0, s, partial, RED_BLOCKS, out_scalars, 0,
+              (float)((long long)H * W), (float)((long long)2 * H * W), (float)(n1 + n2), bound_sq, mu, f_type, 8);
+  PCFA_LAUNCH_CHECK();
+  pcfa_launch(loss_items_total_kernel, dim3(1), dim3(1), 0, s, (const float*)out_scalars, items, out_total);
+  PCFA_LAUNCH_CHECK();
+  return PCFA_OK;
+}
+
+extern "C" int pcfa_flow_loss_items_bwd(const float* pred, const long long pred_strides[4], const float* target,
+                                        const long long target_strides[4], int items, int H, int W, const float* delta1,
+                                        long long n1, const float* delta2, long long n2, float mu, int f_type, int joint,
+                                        const float* fwd_scalars, const float* grad_loss, float* grad_pred,
+                                        float* grad_delta1, float* grad_delta2, void* stream) {
+  if (!pred || !target || !pred_strides || !target_strides || !fwd_scalars || !grad_loss || H < 1 || W < 1 || n1 < 1 ||
+      n2 < 1 || f_type < 0 || f_type > 2)
+    return PCFA_ERR_INVALID_ARG;
+  if (int st = items_status(items)) return st;
+  hipStream_t s = (hipStream_t)stream;
+  if (grad_pred) {
+    const LossItemStride is{pred_strides[0], target_strides[0], 0, 0};
+    pcfa_launch(loss_bwd_flow_kernel, dim3(ew_blocks((long long)H * W), items), dim3(256), 0, s, pred,
+                mkview(pred_strides), target, mkview(target_strides), 1, H, W, f_type, fwd_scalars, grad_loss, grad_pred,
+                is);
+    PCFA_LAUNCH_CHECK();
+  }
+  const float ndelta = (float)(n1 + n2);
+  if (grad_delta1) {
+    if (!delta1) return PCFA_ERR_INVALID_ARG;
+    pcfa_launch(loss_bwd_delta_kernel, dim3(ew_blocks(n1), items), dim3(256), 0, s, delta1, n1, ndelta, mu,
+                joint ? 2.f : 1.f, fwd_scalars, grad_loss, grad_delta1, n1);
+    PCFA_LAUNCH_CHECK();
+  }
+  if (grad_delta2) {
+    if (!delta2) return PCFA_ERR_INVALID_ARG;
+    pcfa_launch(loss_bwd_delta_kernel, dim3(ew_blocks(n2), items), dim3(256), 0, s, delta2, n2, ndelta, mu, 1.f,
+                fwd_scalars, grad_loss, grad_delta2, n2);
     PCFA_LAUNCH_CHECK();
   }
   return PCFA_OK;
@@ -617,10 +720,27 @@ extern "C" int pcfa_avg_epe(const float* flow1, const long long strides1[4], con
   float* partial = (float*)workspace;
   pcfa_launch(loss_partial_kernel, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, s, flow1,
                      mkview(strides1), flow2, mkview(strides2), B, H, W, (const float*)nullptr,
-                     0LL, (const float*)nullptr, 0LL, partial);
+                     0LL, (const float*)nullptr, 0LL, partial, LossItemStride{0, 0, 0, 0});
   PCFA_LAUNCH_CHECK();
   pcfa_launch(loss_final_kernel, dim3(1), dim3(RED_THREADS), 0, s, partial, RED_BLOCKS,
-                     out, 1, (float)((long long)B * H * W), 0.f, 1.f, 0.f, 0.f, 0);
+                     out, 1, (float)((long long)B * H * W), 0.f, 1.f, 0.f, 0.f, 0, 0);
+  PCFA_LAUNCH_CHECK();
+  return PCFA_OK;
+}
+
+extern "C" int pcfa_avg_epe_items(const float* flow1, const long long strides1[4], const float* flow2,
+                                  const long long strides2[4], int items, int H, int W, float* out, void* workspace,
+                                  void* stream) {
+  if (!flow1 || !flow2 || !strides1 || !strides2 || !out || !workspace || H < 1 || W < 1) return PCFA_ERR_INVALID_ARG;
+  if (int st = items_status(items)) return st;
+  hipStream_t s = (hipStream_t)stream;
+  float* partial = (float*)workspace;
+  pcfa_launch(loss_partial_kernel, dim3(RED_BLOCKS, items), dim3(RED_THREADS), 0, s, flow1, mkview(strides1), flow2,
+              mkview(strides2), 1, H, W, (const float*)nullptr, 0LL, (const float*)nullptr, 0LL, partial,
+              LossItemStride{strides1[0], strides2[0], 0, 0});
+  PCFA_LAUNCH_CHECK();
+  pcfa_launch(loss_final_kernel, dim3(1, items), dim3(RED_THREADS), 0, s, partial, RED_BLOCKS, out, 1,
+              (float)((long long)H * W), 0.f, 1.f, 0.f, 0.f, 0, 1);
   PCFA_LAUNCH_CHECK();
   return PCFA_OK;
 }
@@ -632,10 +752,27 @@ extern "C" int pcfa_sum_squares(const float* x, long long n, float* out, void* w
   float* partial = (float*)workspace;
   pcfa_launch(loss_partial_kernel, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, s,
                      (const float*)nullptr, View4{0, 0, 0, 0}, (const float*)nullptr,
-                     View4{0, 0, 0, 0}, 1, 1, 1, x, n, (const float*)nullptr, 0LL, partial);
+                     View4{0, 0, 0, 0}, 1, 1, 1, x, n, (const float*)nullptr, 0LL, partial,
+                     LossItemStride{0, 0, 0, 0});
   PCFA_LAUNCH_CHECK();
   pcfa_launch(loss_final_kernel, dim3(1), dim3(RED_THREADS), 0, s, partial, RED_BLOCKS,
-                     out, 2, 1.f, 1.f, 1.f, 0.f, 0.f, 0);
+                     out, 2, 1.f, 1.f, 1.f, 0.f, 0.f, 0, 0);
+  PCFA_LAUNCH_CHECK();
+  return PCFA_OK;
+}
+
+extern "C" int pcfa_sum_squares_items(const float* x, int items, long long n, float* out, void* workspace,
+                                      void* stream) {
+  if (!x || !out || !workspace || n < 1) return PCFA_ERR_INVALID_ARG;
+  if (int st = items_status(items)) return st;
+  hipStream_t s = (hipStream_t)stream;
+  float* partial = (float*)workspace;
+  pcfa_launch(loss_partial_kernel, dim3(RED_BLOCKS, items), dim3(RED_THREADS), 0, s, (const float*)nullptr,
+              View4{0, 0, 0, 0}, (const float*)nullptr, View4{0, 0, 0, 0}, 1, 1, 1, x, n, (const float*)nullptr, 0LL,
+              partial, LossItemStride{0, 0, n, 0});
+  PCFA_LAUNCH_CHECK();
+  pcfa_launch(loss_final_kernel, dim3(1, items), dim3(RED_THREADS), 0, s, partial, RED_BLOCKS, out, 2, 1.f, 1.f, 1.f,
+              0.f, 0.f, 0, 1);
   PCFA_LAUNCH_CHECK();
   return PCFA_OK;
 }

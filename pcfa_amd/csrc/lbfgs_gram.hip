@@ -42,6 +42,20 @@ __host__ __device__ inline size_t gs_off_SY(int rows) { return gs_off_red(rows) 
 __host__ __device__ inline size_t gs_off_YY(int rows) { return gs_off_SY(rows) + gs_align((size_t)rows * rows * 8); }
 __host__ __device__ inline size_t gs_bytes(int rows) { return gs_off_YY(rows) + gs_align((size_t)rows * rows * 8); }
 
+// ---- several optimisers in one launch ----------------------------------------------------------------------------------
+// The *_items entry points put item b = blockIdx.y of a batch of independent optimisers on the grid's y axis: every base
+// pointer moves by its item stride and the item then runs the very blocks, threads and summation order of the single call
+// (which is a launch with gridDim.y == 1, live = 1).  An item whose `live` bit is clear is neither read nor written.
+struct GramItems {
+  unsigned live;
+  long long vec, hist, state, ws;   // item strides of g / g_prev / d (floats), S / Y (floats), state (bytes), workspace (floats)
+  __device__ __forceinline__ bool skip() const { return !((live >> blockIdx.y) & 1u); }
+};
+struct GramSteps {
+  float t[PCFA_MAX_ITEMS];   // step length per item, by value
+};
+constexpr GramItems GR_SINGLE = {1u, 0, 0, 0, 0};
+
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ float dpp_add(float v) {
   const int x = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false);
@@ -74,10 +88,20 @@ __device__ __forceinline__ void axpy4(float c, const float4& a, float4& x) {
 // y = g - g_prev, s = t d go to the candidate row (first + count) % rows, g_prev = g; for every live row r and the
 // candidate: partial[(r*4 + k) * nblk + block], k = {S_r.g, S_r.y, Y_r.g, Y_r.y}.
 __global__ __launch_bounds__(GR_THREADS) void gram_pass_kernel(
-    const float* __restrict__ g, float* __restrict__ g_prev, const float* __restrict__ d, float t,
-    float* __restrict__ S, float* __restrict__ Y, const GramHeader* __restrict__ hdr, float* __restrict__ partial,
-    int rows, long long ld4, int nblk) {
+    const float* __restrict__ g, float* __restrict__ g_prev, const float* __restrict__ d, GramSteps steps,
+    float* __restrict__ S, float* __restrict__ Y, const unsigned char* __restrict__ state, float* __restrict__ partial,
+    int rows, long long ld4, int nblk, GramItems it) {
   extern __shared__ float4 s_acc[];  // [GR_WAVES][rows]
+  if (it.skip()) return;
+  const long long item = blockIdx.y;
+  g += item * it.vec;
+  g_prev += item * it.vec;
+  d += item * it.vec;
+  S += item * it.hist;
+  Y += item * it.hist;
+  partial += item * it.ws;
+  const GramHeader* hdr = reinterpret_cast<const GramHeader*>(state + item * it.state);
+  const float t = steps.t[item];
   const int first = hdr->first, count = hdr->count;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long i0 = (long long)blockIdx.x * GR_CHUNK4 + threadIdx.x, i1 = i0 + GR_THREADS;
@@ -153,8 +177,13 @@ __device__ __forceinline__ double wave_sum_all_f64(double v) {
 // red[r*4 + k] = sum over the workgroups of sweep 1, in index order per lane, fp64.  One workgroup per ring row,
 // one wave per kind.
 __global__ __launch_bounds__(GR_THREADS) void gram_reduce_kernel(const float* __restrict__ partial,
-                                                                 const GramHeader* __restrict__ hdr,
-                                                                 double* __restrict__ red, int rows, int nblk) {
+                                                                 unsigned char* __restrict__ state, int rows, int nblk,
+                                                                 GramItems it) {
+  if (it.skip()) return;
+  state += (long long)blockIdx.y * it.state;
+  partial += (long long)blockIdx.y * it.ws;
+  const GramHeader* hdr = reinterpret_cast<const GramHeader*>(state);
+  double* red = reinterpret_cast<double*>(state + gs_off_red(rows));
   const int r = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   int k = r - hdr->first;
   if (k < 0) k += rows;
@@ -182,8 +211,10 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {
 }
 
 __global__ __launch_bounds__(GC_THREADS) void gram_coeff_kernel(unsigned char* __restrict__ state, int rows, int cap,
-                                                                int have_candidate) {
+                                                                int have_candidate, GramItems it) {
   extern __shared__ double s_mem[];
+  if (it.skip()) return;
+  state += (long long)blockIdx.y * it.state;
   GramHeader* hdr = reinterpret_cast<GramHeader*>(state);
   float* cS = reinterpret_cast<float*>(state + gs_off_cS(rows));
   float* cY = reinterpret_cast<float*>(state + gs_off_cY(rows));
@@ -363,8 +394,18 @@ __global__ __launch_bounds__(GC_THREADS) void gram_coeff_kernel(unsigned char* _
 __global__ __launch_bounds__(GR_THREADS) void gram_direction_kernel(
     const float* __restrict__ g, const float* __restrict__ S, const float* __restrict__ Y,
     const unsigned char* __restrict__ state, float* __restrict__ d, float* __restrict__ partial, int rows,
-    long long ld4, int nblk) {
+    long long ld4, int nblk, GramItems it) {
   __shared__ float s_red[2 * GR_WAVES];
+  if (it.skip()) return;
+  {
+    const long long item = blockIdx.y;
+    g += item * it.vec;
+    d += item * it.vec;
+    S += item * it.hist;
+    Y += item * it.hist;
+    state += item * it.state;
+    partial += item * it.ws;
+  }
   const GramHeader* hdr = reinterpret_cast<const GramHeader*>(state);
   const float* cS = reinterpret_cast<const float*>(state + gs_off_cS(rows));
   const float* cY = reinterpret_cast<const float*>(state + gs_off_cY(rows));
@@ -426,9 +467,14 @@ __global__ __launch_bounds__(GR_THREADS) void gram_direction_kernel(
 
 __global__ __launch_bounds__(GR_THREADS) void gram_direction_final_kernel(const float* __restrict__ partial,
                                                                           unsigned char* __restrict__ state,
-                                                                          float* __restrict__ out2, int nblk) {
+                                                                          float* __restrict__ out2, int nblk,
+                                                                          GramItems it) {
   __shared__ double s_a[GR_WAVES];
   __shared__ float s_b[GR_WAVES];
+  if (it.skip()) return;
+  partial += (long long)blockIdx.y * it.ws;
+  state += (long long)blockIdx.y * it.state;
+  out2 += 2 * blockIdx.y;
   double a = 0.0;
   float b = 0.f;
   for (int i = threadIdx.x; i < nblk; i += GR_THREADS) {
@@ -459,8 +505,9 @@ __global__ __launch_bounds__(GR_THREADS) void gram_direction_final_kernel(const 
   }
 }
 
-__global__ void gram_reset_kernel(unsigned char* __restrict__ state, int rows) {
-  GramHeader* hdr = reinterpret_cast<GramHeader*>(state);
+__global__ void gram_reset_kernel(unsigned char* __restrict__ state, int rows, GramItems it) {
+  if (it.skip()) return;
+  GramHeader* hdr = reinterpret_cast<GramHeader*>(state + (long long)blockIdx.y * it.state);
   hdr->first = 0;
   hdr->count = 0;
   hdr->accepted = 0;
@@ -486,29 +533,41 @@ extern "C" size_t pcfa_lbfgs_gram_workspace_bytes(int capacity, long long ld) {
   return ((size_t)(capacity + 1) * 4 * nblk + 2 * nblk) * sizeof(float);
 }
 
-extern "C" int pcfa_lbfgs_gram_reset(void* state, int capacity, void* stream) {
+namespace {
+
+int items_status(int items) {
+  if (items < 1) return PCFA_ERR_INVALID_ARG;
+  if (items > PCFA_MAX_ITEMS) return PCFA_ERR_UNSUPPORTED;
+  return PCFA_OK;
+}
+
+// Dense per-item buffers: the item strides follow from capacity and ld.
+GramItems items_of(unsigned live, int capacity, long long ld) {
+  return GramItems{live, ld, (long long)(capacity + 1) * ld, (long long)gs_bytes(capacity + 1),
+                   (long long)(pcfa_lbfgs_gram_workspace_bytes(capacity, ld) / sizeof(float))};
+}
+
+int gram_reset(void* state, int capacity, int items, GramItems it, hipStream_t st) {
   if (!state || capacity < 1 || capacity + 1 > GR_MAX_ROWS) return PCFA_ERR_INVALID_ARG;
-  pcfa_launch(gram_reset_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (unsigned char*)state, capacity + 1);
+  pcfa_launch(gram_reset_kernel, dim3(1, items), dim3(1), 0, st, (unsigned char*)state, capacity + 1, it);
   PCFA_LAUNCH_CHECK();
   return PCFA_OK;
 }
 
-extern "C" int pcfa_lbfgs_gram_update(const float* g, float* g_prev, const float* d, float t, float* S, float* Y,
-                                      void* state, void* workspace, int capacity, long long ld, void* stream) {
+int gram_update(const float* g, float* g_prev, const float* d, const GramSteps& steps, float* S, float* Y, void* state,
+                void* workspace, int capacity, long long ld, int items, GramItems it, hipStream_t st) {
   if (!g || !g_prev || !d || !S || !Y || !state || !workspace || capacity < 1 || ld < 4 || (ld & 3))
     return PCFA_ERR_INVALID_ARG;
   if (capacity + 1 > GR_MAX_ROWS) return PCFA_ERR_UNSUPPORTED;
   if (!aligned16(g) || !aligned16(g_prev) || !aligned16(d) || !aligned16(S) || !aligned16(Y) || !aligned16(state))
     return PCFA_ERR_INVALID_ARG;
   const int rows = capacity + 1, nblk = nblocks_for(ld);
-  hipStream_t st = (hipStream_t)stream;
   unsigned char* sb = (unsigned char*)state;
   float* partial = (float*)workspace;
-  pcfa_launch(gram_pass_kernel, dim3(nblk), dim3(GR_THREADS), (size_t)GR_WAVES * rows * sizeof(float4), st, g, g_prev,
-              d, t, S, Y, (const GramHeader*)sb, partial, rows, ld / 4, nblk);
+  pcfa_launch(gram_pass_kernel, dim3(nblk, items), dim3(GR_THREADS), (size_t)GR_WAVES * rows * sizeof(float4), st, g,
+              g_prev, d, steps, S, Y, (const unsigned char*)sb, partial, rows, ld / 4, nblk, it);
   PCFA_LAUNCH_CHECK();
-  pcfa_launch(gram_reduce_kernel, dim3(rows), dim3(GR_THREADS), 0, st, (const float*)partial, (const GramHeader*)sb,
-              (double*)(sb + gs_off_red(rows)), rows, nblk);
+  pcfa_launch(gram_reduce_kernel, dim3(rows, items), dim3(GR_THREADS), 0, st, (const float*)partial, sb, rows, nblk, it);
   PCFA_LAUNCH_CHECK();
   const size_t lds = ((size_t)capacity * capacity + 4 * (size_t)capacity) * sizeof(double);
   static size_t granted = 0;   // the attribute only ever grows
@@ -518,28 +577,71 @@ extern "C" int pcfa_lbfgs_gram_update(const float* g, float* g_prev, const float
     if (e != hipSuccess) return (int)e;
     granted = lds;
   }
-  pcfa_launch(gram_coeff_kernel, dim3(1), dim3(GC_THREADS), lds, st, sb, rows, capacity, 1);
+  pcfa_launch(gram_coeff_kernel, dim3(1, items), dim3(GC_THREADS), lds, st, sb, rows, capacity, 1, it);
   PCFA_LAUNCH_CHECK();
   return PCFA_OK;
 }
 
-extern "C" int pcfa_lbfgs_gram_direction(const float* g, const float* S, const float* Y, void* state, float* d,
-                                         float* out_gtd_dmax, void* workspace, int capacity, long long ld,
-                                         void* stream) {
+int gram_direction(const float* g, const float* S, const float* Y, void* state, float* d, float* out_gtd_dmax,
+                   void* workspace, int capacity, long long ld, int items, GramItems it, hipStream_t st) {
   if (!g || !S || !Y || !state || !d || !out_gtd_dmax || !workspace || capacity < 1 || ld < 4 || (ld & 3))
     return PCFA_ERR_INVALID_ARG;
   if (capacity + 1 > GR_MAX_ROWS) return PCFA_ERR_UNSUPPORTED;
   if (!aligned16(g) || !aligned16(S) || !aligned16(Y) || !aligned16(d) || !aligned16(state))
     return PCFA_ERR_INVALID_ARG;
   const int rows = capacity + 1, nblk = nblocks_for(ld);
-  hipStream_t st = (hipStream_t)stream;
   unsigned char* sb = (unsigned char*)state;
   float* partial = (float*)workspace + (size_t)rows * 4 * nblk;
-  pcfa_launch(gram_direction_kernel, dim3(nblk), dim3(GR_THREADS), 0, st, g, S, Y, (const unsigned char*)sb, d,
-              partial, rows, ld / 4, nblk);
+  pcfa_launch(gram_direction_kernel, dim3(nblk, items), dim3(GR_THREADS), 0, st, g, S, Y, (const unsigned char*)sb, d,
+              partial, rows, ld / 4, nblk, it);
   PCFA_LAUNCH_CHECK();
-  pcfa_launch(gram_direction_final_kernel, dim3(1), dim3(GR_THREADS), 0, st, (const float*)partial, sb, out_gtd_dmax,
-              nblk);
+  pcfa_launch(gram_direction_final_kernel, dim3(1, items), dim3(GR_THREADS), 0, st, (const float*)partial, sb,
+              out_gtd_dmax, nblk, it);
   PCFA_LAUNCH_CHECK();
   return PCFA_OK;
+}
+
+}  // namespace
+
+extern "C" int pcfa_lbfgs_gram_reset(void* state, int capacity, void* stream) {
+  return gram_reset(state, capacity, 1, GR_SINGLE, (hipStream_t)stream);
+}
+
+extern "C" int pcfa_lbfgs_gram_update(const float* g, float* g_prev, const float* d, float t, float* S, float* Y,
+                                      void* state, void* workspace, int capacity, long long ld, void* stream) {
+  GramSteps steps = {};
+  steps.t[0] = t;
+  return gram_update(g, g_prev, d, steps, S, Y, state, workspace, capacity, ld, 1, GR_SINGLE, (hipStream_t)stream);
+}
+
+extern "C" int pcfa_lbfgs_gram_direction(const float* g, const float* S, const float* Y, void* state, float* d,
+                                         float* out_gtd_dmax, void* workspace, int capacity, long long ld,
+                                         void* stream) {
+  return gram_direction(g, S, Y, state, d, out_gtd_dmax, workspace, capacity, ld, 1, GR_SINGLE, (hipStream_t)stream);
+}
+
+extern "C" int pcfa_lbfgs_gram_reset_items(void* state, int capacity, int items, unsigned mask, void* stream) {
+  if (int e = items_status(items)) return e;
+  if (capacity < 1 || capacity + 1 > GR_MAX_ROWS) return PCFA_ERR_INVALID_ARG;
+  return gram_reset(state, capacity, items, items_of(mask, capacity, 4), (hipStream_t)stream);
+}
+
+extern "C" int pcfa_lbfgs_gram_update_items(const float* g, float* g_prev, const float* d, const float* t, float* S,
+                                            float* Y, void* state, void* workspace, int capacity, long long ld,
+                                            int items, unsigned live, void* stream) {
+  if (int e = items_status(items)) return e;
+  if (!t || capacity < 1 || capacity + 1 > GR_MAX_ROWS || ld < 4 || (ld & 3)) return PCFA_ERR_INVALID_ARG;
+  GramSteps steps = {};
+  for (int b = 0; b < items; ++b) steps.t[b] = t[b];
+  return gram_update(g, g_prev, d, steps, S, Y, state, workspace, capacity, ld, items, items_of(live, capacity, ld),
+                     (hipStream_t)stream);
+}
+
+extern "C" int pcfa_lbfgs_gram_direction_items(const float* g, const float* S, const float* Y, void* state, float* d,
+                                               float* out_gtd_dmax, void* workspace, int capacity, long long ld,
+                                               int items, unsigned live, void* stream) {
+  if (int e = items_status(items)) return e;
+  if (capacity < 1 || capacity + 1 > GR_MAX_ROWS || ld < 4 || (ld & 3)) return PCFA_ERR_INVALID_ARG;
+  return gram_direction(g, S, Y, state, d, out_gtd_dmax, workspace, capacity, ld, items, items_of(live, capacity, ld),
+                        (hipStream_t)stream);
 }

@@ -49,6 +49,10 @@ _FLAGS = [
     ("pcfa", "--batch_size", dict(default=4, type=int, help="[universal only] pairs per batch"), _PCFA),
     ("pcfa", "--pairs_in_flight", dict(default=1, type=int, help="NEW: independent pairs attacked side by side on every "
                                        "GPU (per-pair mode; results identical to 1, ~1.3x the pairs/s at 2)"), _PCFA_TRAIN),
+    ("pcfa", "--pairs_per_closure", dict(default=1, type=int, help="NEW: independent pairs of one shape attacked in one "
+                                         "batched closure on every GPU (per-pair mode; one forward/backward at batch B, "
+                                         "per-pair variables, target, L-BFGS state and best iterate; not with "
+                                         "--pairs_in_flight > 1)"), _PCFA_TRAIN),
     ("pcfa", "--delta_bound", dict(default=0.005, type=float, help="bound on the per-pixel averaged L2 norm of "
                                    "the perturbation"), _PCFA_TRAIN),
     ("pcfa", "--mu", dict(default=-1, type=float, help="penalty weight; -1 = 2500/delta_bound (x1.5 for non-zero "

@@ -23,6 +23,8 @@ the vector work runs:
 There is no CPU path: CPU tensors raise (tests drive the host logic of the attack with the oracle's optimiser, which is
 torch.optim.LBFGS itself).
 """
+import ctypes
+
 import numpy as np
 import torch
 from torch.optim import Optimizer
@@ -262,4 +264,208 @@ class LBFGS(Optimizer):
 
         state["t"] = t
         state["prev_loss"] = prev_loss
+        return orig_loss
+
+
+class BatchedLBFGS:
+    """`items` independent L-BFGS optimisers (Gram form) that share every closure evaluation and every launch.
+
+    Every parameter has leading dimension B = items; item b's vector is the concatenation of ``p[b]`` over the parameters.
+    ``step(closure)`` calls ``closure()`` once for all items -- it leaves ``p.grad`` [B, ...] behind and returns the B
+    losses (a static buffer is fine) -- and takes, per item, every host decision of ``LBFGS.step`` from the same
+    quantities in the same order, so item b's iterates are those of a solo ``LBFGS`` on ``p[b]`` bit for bit as long as
+    the closure is item-separable: the vector kernels are the solo ones with the item on the grid's y axis
+    (pcfa_lbfgs_gram_*_items), the first iteration's |g|_1 and g.d and the variable update are the solo optimiser's ATen
+    ops on the item's row.  An item that stops inside a ``step()`` is frozen until the next ``step()``: its variables,
+    history, g_prev and state are untouched (the kernels skip it) while its batch-mates go on and the closure keeps
+    evaluating everybody.  Two host reads per trip for all items together: ``host_syncs`` does not depend on B."""
+
+    def __init__(self, params, items, lr=1, max_iter=20, max_eval=None, tolerance_grad=1e-7, tolerance_change=1e-9,
+                 history_size=100):
+        self._params = list(params)
+        self.items = int(items)
+        if not 1 <= self.items <= _hip.MAX_ITEMS:
+            raise ValueError("BatchedLBFGS: 1 to %d items, got %d" % (_hip.MAX_ITEMS, self.items))
+        if history_size > 128:
+            raise ValueError("BatchedLBFGS runs the Gram form only (history_size <= 128)")
+        if not self._params:
+            raise ValueError("BatchedLBFGS got an empty parameter list")
+        for p in self._params:
+            if not p.is_cuda or p.dtype != torch.float32:
+                raise RuntimeError("pcfa_amd.lbfgs.BatchedLBFGS needs float32 GPU parameters (no CPU fallback)")
+            if p.dim() < 1 or p.shape[0] != self.items or not p.is_contiguous():
+                raise ValueError("every parameter is dense with leading dimension items=%d, got %s"
+                                 % (self.items, tuple(p.shape)))
+        if max_eval is None:
+            max_eval = max_iter * 5 // 4
+        self.defaults = dict(lr=lr, max_iter=max_iter, max_eval=max_eval, tolerance_grad=tolerance_grad,
+                             tolerance_change=tolerance_change, history_size=history_size)
+        self._n = sum(p.numel() // self.items for p in self._params)
+        self._ld = (self._n + 3) // 4 * 4
+        self._bufs = None
+        self.state = [{} for _ in range(self.items)]
+        self.host_syncs = 0
+
+    def _buffers(self):
+        if self._bufs is None:
+            dev, B, cap = self._params[0].device, self.items, self.defaults["history_size"]
+            lib = _hip.load()
+            f32 = dict(dtype=torch.float32, device=dev)
+            self._bufs = {
+                # as in LBFGS, one row per item: the ld - n pad elements stay zero
+                "g": torch.zeros(B, self._ld, **f32), "g_prev": torch.zeros(B, self._ld, **f32),
+                "d": torch.zeros(B, self._ld, **f32),
+                "S": torch.empty(B, cap + 1, self._ld, **f32), "Y": torch.empty(B, cap + 1, self._ld, **f32),
+                "ws": torch.empty(B, int(lib.pcfa_lbfgs_gram_workspace_bytes(cap, self._ld)) // 4, **f32),
+                "state": torch.zeros(B, int(lib.pcfa_lbfgs_gram_state_bytes(cap)), dtype=torch.uint8, device=dev),
+                "out2": torch.zeros(B, 2, **f32),
+            }
+        return self._bufs
+
+    def reset(self):
+        """Forget every item's history and iteration state (new image pairs on the same variables and buffers)."""
+        self.state = [{} for _ in range(self.items)]
+        self.host_syncs = 0
+
+    def history_count(self, b):
+        """Pairs currently in item b's history; a host read."""
+        if self._bufs is None or self.state[b].get("n_iter", 0) == 0:
+            return 0
+        return int(self._bufs["state"][b, :16].view(torch.int32)[1])
+
+    def flat_grad_views(self):
+        """One [B, ...] view per parameter into the optimiser's gradient rows (row pitch ld, so the views are strided in
+        the item dimension).  A closure that leaves `p.grad` pointing at them spares the gather copies."""
+        g, off, views = self._buffers()["g"], 0, []
+        for p in self._params:
+            n = p.numel() // self.items
+            views.append(g[:, off:off + n].view(p.shape))
+            off += n
+        return views
+
+    def _gather_flat_grad(self, g):
+        off = 0
+        for p in self._params:
+            n = p.numel() // self.items
+            dst = g[:, off:off + n]
+            if p.grad is None:
+                dst.zero_()
+            elif (p.grad.data_ptr() == dst.data_ptr() and p.grad[0].is_contiguous()
+                  and (self.items == 1 or p.grad.stride(0) == self._ld)):
+                pass                                   # already in place (closure with grad_sink)
+            else:
+                dst.copy_(p.grad.reshape(self.items, n))   # one strided copy per parameter
+            off += n
+
+    def _add_grad(self, b, step_size, drow):
+        off = 0
+        for p in self._params:      # LBFGS._add_grad on item b's slices: the same ATen op, hence the same rounding
+            n = p.numel() // self.items
+            p[b].add_(drow[off:off + n].view_as(p[b]), alpha=step_size)
+            off += n
+
+    def _read(self, *tensors):
+        self.host_syncs += 1
+        return torch.cat([t.detach().reshape(-1).to(torch.float32) for t in tensors]).tolist()
+
+    @torch.no_grad()
+    def step(self, closure):
+        closure = torch.enable_grad()(closure)
+        o = self.defaults
+        lr, max_iter, max_eval = float(o["lr"]), o["max_iter"], o["max_eval"]
+        tolerance_change = o["tolerance_change"]
+        tol_grad32 = float(np.float32(o["tolerance_grad"]))
+        tol_change32 = float(np.float32(tolerance_change))
+        cap, nb, n, ld = o["history_size"], self.items, self._n, self._ld
+        buf = self._buffers()
+        G, D = buf["g"], buf["d"]
+        p = lambda t: t.data_ptr()  # noqa: E731
+        mask = lambda items: sum(1 << b for b in items)  # noqa: E731
+        absmax_rows = lambda: torch.linalg.vector_norm(G[:, :n], float("inf"), dim=1)  # noqa: E731 (a max: order-free)
+
+        for st in self.state:
+            st.setdefault("func_evals", 0)
+            st.setdefault("n_iter", 0)
+
+        orig_loss = closure().detach().reshape(nb).clone()   # the values of THIS evaluation, as torch returns them
+        current_evals = 1
+        for st in self.state:
+            st["func_evals"] += 1
+        self._gather_flat_grad(G)
+        vals = self._read(orig_loss, absmax_rows())
+        loss = vals[:nb]
+        live = [b for b in range(nb) if not vals[nb + b] <= tol_grad32]
+        t = [self.state[b].get("t") for b in range(nb)]
+        prev_loss = [self.state[b].get("prev_loss") for b in range(nb)]
+        d_absmax = [0.0] * nb
+        entered = list(live)
+
+        n_iter = 0
+        while live and n_iter < max_iter:
+            n_iter += 1
+            first, update = [], []
+            for b in live:
+                self.state[b]["n_iter"] += 1
+                (first if self.state[b]["n_iter"] == 1 else update).append(b)
+
+            # ---- direction -----------------------------------------------------------------------------------
+            for b in first:
+                torch.neg(G[b, :n], out=D[b, :n])
+                buf["g_prev"][b, :n].copy_(G[b, :n])
+            if first:
+                _call("pcfa_lbfgs_gram_reset_items", p(buf["state"]), cap, nb, mask(first))
+            if update:
+                steps = (ctypes.c_float * nb)(*[float(t[b]) if b in update else 0.0 for b in range(nb)])
+                _call("pcfa_lbfgs_gram_update_items", p(G), p(buf["g_prev"]), p(D), steps, p(buf["S"]), p(buf["Y"]),
+                      p(buf["state"]), p(buf["ws"]), cap, ld, nb, mask(update))
+                _call("pcfa_lbfgs_gram_direction_items", p(G), p(buf["S"]), p(buf["Y"]), p(buf["state"]), p(D),
+                      p(buf["out2"]), p(buf["ws"]), cap, ld, nb, mask(update))
+            for b in live:
+                prev_loss[b] = loss[b]
+
+            # ---- step lengths + directional derivatives: ONE host synchronisation for all items ----------------
+            # (a first iteration takes g.d, max|d| and |g|_1 from the solo optimiser's ATen reductions on its row)
+            firsts = [torch.stack((G[b, :n].dot(D[b, :n]), torch.linalg.vector_norm(D[b, :n], float("inf")),
+                                   G[b, :n].abs().sum())) for b in first]
+            vals = self._read(buf["out2"], *firsts)
+            go = []
+            for b in live:
+                if b in first:
+                    k = 2 * nb + 3 * first.index(b)
+                    gtd, d_absmax[b], g_abssum = vals[k:k + 3]
+                    t[b] = min(1.0, float(np.float32(1.0) / np.float32(g_abssum))) * lr   # fp32 reciprocal, as torch's
+                else:
+                    gtd, d_absmax[b] = vals[2 * b:2 * b + 2]
+                    t[b] = lr
+                if not gtd > -tolerance_change:
+                    go.append(b)
+            live = go
+            for b in live:
+                self._add_grad(b, t[b], D[b])
+            if n_iter == max_iter or not live:
+                break
+
+            losses_t = closure()
+            self._gather_flat_grad(G)
+            vals = self._read(losses_t.detach().reshape(nb), absmax_rows())
+            current_evals += 1
+            go = []
+            for b in live:
+                self.state[b]["func_evals"] += 1
+                loss[b] = vals[b]
+                # ---- stopping rules, in LBFGS.step's order ---------------------------------------------------
+                if current_evals >= max_eval:
+                    continue
+                if vals[nb + b] <= tol_grad32:
+                    continue
+                if float(np.float32(d_absmax[b]) * np.float32(abs(t[b]))) <= tol_change32:
+                    continue
+                if abs(loss[b] - prev_loss[b]) < tolerance_change:
+                    continue
+                go.append(b)
+            live = go
+
+        for b in entered:
+            self.state[b]["t"] = t[b]
+            self.state[b]["prev_loss"] = prev_loss[b]
         return orig_loss

@@ -61,6 +61,8 @@ class _BoxTransform(torch.autograd.Function):
         d = None if delta is None else delta.contiguous()
         B = img.shape[0]
         n = img.numel() // B
+        if d is not None and B > 1 and d.numel() == img.numel():
+            B, n = 1, img.numel()   # one delta per item (attack_PCFA.PairBatch): element-wise, i.e. one flat sample
         if d is not None and d.numel() != n:
             raise ValueError("delta must broadcast over the batch: %s vs %s" % (tuple(d.shape), tuple(img.shape)))
         out = torch.empty_like(img)
@@ -163,20 +165,22 @@ def fgsm_step(x1, x2, g1, g2, image1, image2, d1, d2, epsilon, joint):
 _WS = {}
 
 
-def _workspace(device):
-    """Reduction scratch of the loss / metric kernels (32 KB), one per (device, stream, lane), allocated once.
+def _workspace(device, items=False):
+    """Reduction scratch of the loss / metric kernels (32 KB; items=True: 32 KB for each of _hip.MAX_ITEMS items, a
+    buffer of its own), one per (device, stream, lane), allocated once.
     While a hipGraph is being captured the capture stream reuses a buffer that was allocated OUTSIDE any capture
     (every capture in this package is preceded by eager warm-up calls on the same device), so no scratch comes from --
     and pins -- a graph's private memory pool; the kernels of one closure are stream-ordered on one stream at a time."""
     idx = device.index if device.index is not None else torch.cuda.current_device()
     capturing = torch.cuda.is_current_stream_capturing()
     ln = current_lane()
-    key = (idx, None if capturing else torch.cuda.current_stream().cuda_stream, ln)
+    key = (idx, None if capturing else torch.cuda.current_stream().cuda_stream, ln) + ((True,) if items else ())
     ws = _WS.get(key)
     if ws is None and capturing:
-        ws = next((w for (d, s_, l_), w in _WS.items() if d == idx and s_ is not None and l_ == ln), None)
+        ws = next((w for k, w in _WS.items() if len(k) == len(key) and k[0] == idx and k[1] is not None and k[2] == ln),
+                  None)
     if ws is None:
-        nbytes = _hip.load().pcfa_flow_loss_workspace_bytes()
+        nbytes = _hip.load().pcfa_flow_loss_workspace_bytes() * (_hip.MAX_ITEMS if items else 1)
         ws = torch.empty(nbytes // 4, device=device, dtype=torch.float32)
         _WS[key] = ws
     return ws
@@ -309,3 +313,93 @@ def two_norm_avg_delta(delta1, delta2):
     """helper_functions/losses.py:91-107."""
     sqrt_numels = (torch.numel(delta1) + torch.numel(delta2)) ** 0.5
     return torch.sqrt(sum_squares(delta1) + sum_squares(delta2)) / sqrt_numels
+
+
+# --------------------------------------------------------------------------- #
+# B independent attacks in one closure: per-item loss and metrics
+# --------------------------------------------------------------------------- #
+def _check_items(B):
+    if not 1 <= B <= _hip.MAX_ITEMS:
+        raise ValueError("1 to %d items per call, got %d" % (_hip.MAX_ITEMS, B))
+
+
+class _LossDeltaConstraintItems(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, delta1, delta2, delta_bound, mu, f_type):
+        _dev(pred, target, delta1, delta2)
+        p, t = _flow4(pred), _flow4(target)
+        if p.shape != t.shape:
+            raise ValueError("pred/target shape mismatch: %s vs %s" % (tuple(p.shape), tuple(t.shape)))
+        B, _, H, W = p.shape
+        _check_items(B)
+        if delta1.shape[0] != B or delta2.shape[0] != B:
+            raise ValueError("one delta per item: pred %s, delta1 %s, delta2 %s"
+                             % (tuple(p.shape), tuple(delta1.shape), tuple(delta2.shape)))
+        d1, d2 = delta1.contiguous(), delta2.contiguous()
+        n1, n2 = d1.numel() // B, d2.numel() // B
+        scal = torch.empty((B, 8), device=p.device, dtype=torch.float32)
+        total = torch.empty((), device=p.device, dtype=torch.float32)
+        ft = _hip.PCFA_LOSS[f_type]
+        _call("pcfa_flow_loss_items_fwd", _ptr(p), _hip.strides4(p), _ptr(t), _hip.strides4(t), B, H, W, _ptr(d1), n1,
+              _ptr(d2), n2, float(delta_bound), float(mu), ft, _ptr(scal), _ptr(total), _ptr(_workspace(p.device, True)))
+        ctx.joint = d1.data_ptr() == d2.data_ptr() and n1 == n2
+        ctx.args = (B, H, W, n1, n2, float(mu), ft)
+        ctx.save_for_backward(p, t, d1, d2, scal)
+        losses = scal[:, 0].clone()
+        ctx.mark_non_differentiable(losses)
+        return total, losses
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_total, _grad_losses):
+        p, t, d1, d2, scal = ctx.saved_tensors
+        B, H, W, n1, n2, mu, ft = ctx.args
+        gl = grad_total.contiguous().reshape(1)
+        need_p, need_d1, need_d2 = ctx.needs_input_grad[0], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        gp = torch.empty((B, 2, H, W), device=p.device, dtype=torch.float32) if need_p else None
+        gd1 = torch.empty_like(d1) if need_d1 else None
+        gd2 = torch.empty_like(d2) if (need_d2 and not ctx.joint) else None
+        if ctx.joint and need_d2 and gd1 is None:
+            gd1 = torch.empty_like(d1)
+        _call("pcfa_flow_loss_items_bwd", _ptr(p), _hip.strides4(p), _ptr(t), _hip.strides4(t), B, H, W, _ptr(d1), n1,
+              _ptr(d2), n2, mu, ft, 0, _ptr(scal), _ptr(gl), _ptr(gp), _ptr(gd1), _ptr(gd2))
+        if ctx.joint:   # the same tensor in both slots: autograd adds them, as in _LossDeltaConstraint
+            return gp, None, (gd1 if need_d1 else None), (gd1 if need_d2 else None), None, None, None
+        return gp, None, gd1, gd2, None, None, None
+
+
+def loss_delta_constraint_items(pred, target, delta1, delta2, delta_bound=0.001, mu=100., f_type="aee"):
+    """loss_delta_constraint for B independent attacks in one autograd node: item b's loss is
+    loss_delta_constraint(pred[b], target[b], delta1[b], delta2[b]) bit for bit (its own H x W, its own deltas, its own
+    relu tie).  Returns (total, losses): total = the in-order fp32 sum of the B losses, the thing to call backward() on --
+    item b's variables enter only L_b, so d(total)/d(x_b) = dL_b/dx_b exactly; losses [B] carries no gradient.
+    pred / target [B,2,H,W] (views are fine), delta1 / delta2 [B,...]; a joint perturbation passes one tensor twice."""
+    if f_type not in _hip.PCFA_LOSS:
+        raise NotImplementedError(
+            "The requested loss type %s does not exist. Please choose one of 'aee', 'mse' or 'cosim'" % f_type)
+    return _LossDeltaConstraintItems.apply(pred, target, delta1, delta2, delta_bound, mu, f_type)
+
+
+def avg_epe_items(flow1, flow2):
+    """[B] values, avg_epe(flow1[b], flow2[b]) each, from one launch pair (metric use: no gradient)."""
+    _dev(flow1, flow2)
+    a, b = _flow4(flow1.detach()), _flow4(flow2.detach())
+    if a.shape != b.shape:
+        raise ValueError("flow shape mismatch")
+    B, _, H, W = a.shape
+    _check_items(B)
+    out = torch.empty(B, device=a.device, dtype=torch.float32)
+    _call("pcfa_avg_epe_items", _ptr(a), _hip.strides4(a), _ptr(b), _hip.strides4(b), B, H, W, _ptr(out),
+          _ptr(_workspace(a.device, True)))
+    return out
+
+
+def sum_squares_items(x):
+    """[B] values, sum_squares(x[b]) each, from one launch pair."""
+    _dev(x)
+    xc = x.detach().contiguous()
+    B = xc.shape[0]
+    _check_items(B)
+    out = torch.empty(B, device=xc.device, dtype=torch.float32)
+    _call("pcfa_sum_squares_items", _ptr(xc), B, xc.numel() // B, _ptr(out), _ptr(_workspace(xc.device, True)))
+    return out

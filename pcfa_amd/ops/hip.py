@@ -25,6 +25,7 @@ Operator boundaries mirrored (reference file:line) -- one module per group:
 """
 from .. import _hip  # noqa: F401
 from ..lbfgs import LBFGS  # noqa: F401  (the attack loop's optimiser: torch.optim.LBFGS semantics, HIP vector math)
+from ..lbfgs import BatchedLBFGS  # noqa: F401  (B of them sharing every closure evaluation: attack_PCFA.PairBatch)
 from .attack_math import *  # noqa: F401,F403
 from .attack_math import _ExtractDeltas  # noqa: F401  (tests / tools reach a few private names through the table)
 from .conv import *  # noqa: F401,F403
