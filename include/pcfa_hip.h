@@ -124,12 +124,20 @@ PCFA_API int pcfa_corr_pyramid_bwd(const float* dpyr, const float* fmap1, const 
 /* The same backward with the lookups' coordinates: dpyr is zero outside the (2r+2)^2 windows its lookups touched
  * (CorrBlock.__call__, models/raft/corr.py:29-50 -- 12 lookups per RAFT forward, all near the diagonal of the 4D
  * volume), so both products skip the slab-column / query-row ranges no window reaches (per 128-wide block, bounding
- * rows of the windows of ALL given lookups, one texel of slack: conservative for any coordinates).  `coords`: host
+ * rows of the windows of ALL given lookups -- for df2ext also their bounding columns, per run of 16 queries -- one texel
+ * of slack: conservative for any coordinates).  `coords`: host
  * array of n_coords (<= 32) device pointers to [B][2][H][W] coordinate tensors -- every lookup whose backward
  * accumulated into dpyr; n_coords = 0 (or misaligned operands) computes the dense products of pcfa_corr_pyramid_bwd.
  * Results are those of the dense form up to the summation order of the split-K partials (the skipped terms are exact
  * zeros); deterministic.  workspace >= pcfa_corr_pyramid_bwd_windows_workspace_bytes(). */
 PCFA_API size_t pcfa_corr_pyramid_bwd_windows_workspace_bytes(int B, int D, int H, int W, int num_levels);
+/* Shape of the K-segment tables pcfa_corr_pyramid_bwd_windows leaves in its workspace, behind the 16-B aligned split-K
+ * area of pcfa_corr_pyramid_bwd_workspace_bytes() (work accounting, tests): out[0] ints per record = { count, widening
+ * taken, hull begin, hull end, (begin, end) x capacity }, out[1] / out[2] records per batch item of table A (128-wide
+ * blocks of dfmap1's queries) / B (128-wide blocks of df2ext's slab columns), stored [B][out[1]] then [B][out[2]];
+ * out[3] the queries per run where table B is clipped in x as well (0: both tables clipped in y only); out[4] the
+ * longest list before it is widened.  Table B's splits share the hull, so its sums do not depend on the clipping. */
+PCFA_API int pcfa_corr_pyramid_bwd_windows_tables(int H, int W, int num_levels, int* out);
 PCFA_API int pcfa_corr_pyramid_bwd_windows(const float* dpyr, const float* fmap1, const float* f2ext, float* dfmap1,
                                   float* dfmap2, void* workspace, size_t workspace_bytes,
                                   const float* const* coords, int n_coords, int radius, int B, int D, int H, int W,

@@ -202,11 +202,30 @@ __device__ __forceinline__ void tile_load_unpool(const float* __restrict__ X, lo
   }
 }
 
-// SPARSE: the K range of a column block is a list of up to four segments (multiples of BK, ascending, read from
+// SPARSE: the K range of a column block is a counted list of segments (multiples of BK, ascending, disjoint, read from
 // segs[(batch * gridDim.x + column block) * SEG_INTS]) instead of [0, K): the backward products of the correlation
-// pyramid skip the part of dpyr that no lookup window ever touched (corr_window_segments_kernel below).  The splits
-// share the ACTIVE steps of a block evenly.
-constexpr int SEG_INTS = 10;   // { count, (begin, end) x 4, pad }
+// pyramid skip the part of dpyr that no lookup window ever touched (the corr_window_* kernels below).
+//   dfmap1 (B stored [N][K]): the splits share the ACTIVE steps of a block evenly.
+//   df2ext (B stored [K][N]): the splits share the steps of the record's HULL evenly and each walks the segments inside
+//     its share.  The hull is the one range of query rows the block had before its list was clipped in x, so every
+//     partial sum keeps its terms (the clipped ones are exact zeros) and the finish adds the same eight numbers.
+constexpr int SEG_CAP = 48;                 // longest list of a block (RAFT at 436x1024: 4 for dfmap1, 33 for df2ext)
+constexpr int SEG_INTS = 4 + 2 * SEG_CAP;   // { count, widening taken, hull begin, hull end, (begin, end) x SEG_CAP }
+constexpr int RUN = 16;                     // queries per entry of the runs table
+
+// Workgroup order of df2ext's sparse product.  Its K chains differ by an order of magnitude: a block of level-0 columns is
+// reached by a few query rows, a block of the coarse levels (the LAST column blocks) by every query.  Workgroups start in
+// the order of their linear id, so the last column blocks get the first ids -- dealt out in the usual order the long
+// chains start last and the launch ends on them alone.  The M blocks and splits of one column block keep consecutive
+// ids (splits fastest: with 8 splits the M blocks that share a dpyr tile land on the same XCD).
+__device__ __forceinline__ void sparse_longest_first(int& by, int& bx, int& bz) {
+  const int nx = gridDim.x, ny = gridDim.y, nz = gridDim.z;
+  const int id = (blockIdx.z * ny + blockIdx.y) * nx + blockIdx.x, rest = id % (ny * nz);
+  bx = nx - 1 - id / (ny * nz);
+  by = rest / nz;
+  bz = rest - by * nz;
+}
+
 template <bool A_KM, bool B_KN, bool FAST, bool POOL, bool UNPOOL = false, bool SPARSE = false>
 __device__ __forceinline__ void gemm_f32_mfma_body(
     const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ C, int M,
@@ -223,15 +242,16 @@ __device__ __forceinline__ void gemm_f32_mfma_body(
   float (*sA)[BK * SA] = reinterpret_cast<float (*)[BK * SA]>(smem);
   float (*sB)[BK * SB] = reinterpret_cast<float (*)[BK * SB]>(smem + 2 * BK * SA);
 
-  const int batch = blockIdx.z / splits;
-  const int split = blockIdx.z - batch * splits;
+  int by = blockIdx.y, bx = blockIdx.x, bz = blockIdx.z;
+  if (SPARSE && B_KN) sparse_longest_first(by, bx, bz);
+  else gemm_tile_xcd_order(by, bx);
+  const int batch = bz / splits;
+  const int split = bz - batch * splits;
   A += batch * bsA;
   B += batch * bsB;
   C += batch * bsC + split * ssC;
   int kbeg = split * kchunk;
   const int kend = SPARSE ? K : min(K, kbeg + kchunk);
-  int by = blockIdx.y, bx = blockIdx.x;
-  gemm_tile_xcd_order(by, bx);
   const int m0 = by * BM;
   int n0 = bx * BN;
   bool pooled = false;
@@ -258,24 +278,42 @@ __device__ __forceinline__ void gemm_f32_mfma_body(
 
   float4 ra[NLD], rb[NLD];
   int nk = (kend - kbeg + BK - 1) / BK;
-  int sb[4] = {0, 0, 0, 0}, se[4] = {0, 0, 0, 0}, seg = 0;
+  const int* sg = nullptr;   // this block's record
+  int nseg = 0, seg = 0, send = 0;
   if (SPARSE) {
-    const int* sg = segs + ((long long)batch * gridDim.x + bx) * SEG_INTS;
-    int total = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      sb[i] = sg[1 + 2 * i];
-      se[i] = sg[2 + 2 * i];
-      total += (se[i] - sb[i]) / BK;
+    sg = segs + ((long long)batch * gridDim.x + bx) * SEG_INTS;
+    nseg = min(sg[0], SEG_CAP);
+    if (!B_KN) {
+      int total = 0;
+      for (int i = 0; i < nseg; ++i) total += (sg[5 + 2 * i] - sg[4 + 2 * i]) / BK;
+      const int t0 = (int)((long long)total * split / splits), t1 = (int)((long long)total * (split + 1) / splits);
+      nk = t1 - t0;
+      if (nk > 0) {   // (total > 0, so nseg > 0)
+        int rem = t0, sbeg = sg[4];
+        send = sg[5];
+        while (seg + 1 < nseg && rem >= (send - sbeg) / BK) {
+          rem -= (send - sbeg) / BK;
+          ++seg;
+          sbeg = sg[4 + 2 * seg];
+          send = sg[5 + 2 * seg];
+        }
+        kbeg = sbeg + rem * BK;   // first stage of this split
+      }
+    } else {
+      const int total = (sg[3] - sg[2]) / BK;
+      const int kb0 = sg[2] + (int)((long long)total * split / splits) * BK;
+      const int kb1 = sg[2] + (int)((long long)total * (split + 1) / splits) * BK;
+      nk = 0;
+      for (int i = nseg - 1; i >= 0; --i) {   // the steps of the segments inside [kb0, kb1); the first of them
+        const int b = max(sg[4 + 2 * i], kb0), e = min(sg[5 + 2 * i], kb1);
+        if (e > b) {
+          nk += (e - b) / BK;
+          seg = i;
+          kbeg = b;
+          send = sg[5 + 2 * i];
+        }
+      }
     }
-    const int t0 = (int)((long long)total * split / splits), t1 = (int)((long long)total * (split + 1) / splits);
-    nk = t1 - t0;
-    int rem = t0;
-    while (seg < 3 && rem >= (se[seg] - sb[seg]) / BK) {
-      rem -= (se[seg] - sb[seg]) / BK;
-      ++seg;
-    }
-    kbeg = sb[seg] + rem * BK;   // first stage of this split
   }
   int kcur = kbeg;
   if (nk > 0) {
@@ -299,9 +337,10 @@ __device__ __forceinline__ void gemm_f32_mfma_body(
     int k0 = kbeg + (kt + 1) * BK;
     if (SPARSE) {   // next stage: the following step of the segment, or the first step of the next non-empty segment
       k0 = kcur + BK;
-      if (k0 >= se[seg] && seg < 3 && se[seg + 1] > sb[seg + 1]) {
+      if (k0 >= send && seg + 1 < nseg) {
         ++seg;
-        k0 = sb[seg];
+        k0 = sg[4 + 2 * seg];
+        send = sg[5 + 2 * seg];
       }
       kcur = k0;
     }
@@ -487,7 +526,10 @@ size_t pooled_lds_bytes(const PyrLayout& P) {
   return n * sizeof(float);
 }
 
-constexpr int BWD_SPLITS = 8;
+#ifndef PCFA_PYRAMID_BWD_SPLITS
+#define PCFA_PYRAMID_BWD_SPLITS 8      // tools/dev A/B (a launch-time constant: the segment tables are built on the device)
+#endif
+constexpr int BWD_SPLITS = PCFA_PYRAMID_BWD_SPLITS;
 constexpr int MAX_COORDS = 32;
 
 struct CoordList {
@@ -504,6 +546,8 @@ struct CoordList {
 //   segB[b][column block j]: the range of query rows that can have touched the block's slab columns
 //                            (one K segment of  df2ext = fmap1 . dpyr).
 // Two small launches: the rows (workgroup per query row), then the two tables (thread per block).
+// This form clips the windows in y only; for df2ext it serves the maps whose width is no multiple of RUN (and very tall
+// ones).  Everywhere else df2ext's lists are clipped in x as well (further below): same record, same GEMM kernels.
 // Step 1: one workgroup per (batch item, query row): min / max of cy over the row's queries and all lookups -> the
 // texel rows of every level the row's windows can have touched (rows table [B][L][H][2] in the workspace).
 __global__ __launch_bounds__(256) void corr_window_rows_kernel(CoordList cl, int H, int W, int r, PyrLayout P,
@@ -544,6 +588,44 @@ __global__ __launch_bounds__(256) void corr_window_rows_kernel(CoordList cl, int
   }
 }
 
+// Record of table A for query block j = queries [128 j, 128 j + 127] = query rows qa..qb: per level the whole tile rows
+// their windows can have touched, adjacent ones merged.
+__device__ __forceinline__ void window_record_a(const int* __restrict__ s_rows, int j, int H, int W, const PyrLayout& P,
+                                                int* __restrict__ o) {
+  const int qa = (j * BN) / W, qb = min((j * BN + BN - 1) / W, H - 1);
+  int n = 0;
+  for (int l = 0; l < P.L; ++l) {
+    int ylo = 1 << 30, yhi = -1;
+    for (int qy = qa; qy <= qb; ++qy) {
+      const int a = s_rows[(l * H + qy) * 2], c = s_rows[(l * H + qy) * 2 + 1];
+      if (a <= c) { ylo = min(ylo, a); yhi = max(yhi, c); }
+    }
+    if (ylo <= yhi) {
+      const int beg = P.off[l] + (ylo >> 2) * P.tw[l] * 16, end = P.off[l] + ((yhi >> 2) + 1) * P.tw[l] * 16;
+      if (n > 0 && o[3 + 2 * n] == beg) o[3 + 2 * n] = end;   // adjacent to the previous segment: merge
+      else { o[4 + 2 * n] = beg; o[5 + 2 * n] = end; ++n; }
+    }
+  }
+  o[0] = n;
+  o[1] = 0;
+  o[2] = o[3] = 0;   // (dfmap1's splits share the active steps: no hull)
+}
+
+// Does query row qy reach column block [ca, cb] going by the rows table (windows clipped in y only)?
+__device__ __forceinline__ bool window_row_reaches(const int* __restrict__ s_rows, int qy, int ca, int cb, int H,
+                                                   const PyrLayout& P) {
+  bool hit = false;
+  for (int l = 0; l < P.L; ++l) {
+    const int lbeg = P.off[l], lend = (l + 1 < P.L ? P.off[l + 1] : P.zero) - 1;
+    const int a = max(ca, lbeg), c = min(cb, lend);
+    if (a > c) continue;
+    const int ya = ((a - lbeg) / (P.tw[l] * 16)) * 4, yb = ((c - lbeg) / (P.tw[l] * 16)) * 4 + 3;   // texel rows
+    const int ra = s_rows[(l * H + qy) * 2], rc = s_rows[(l * H + qy) * 2 + 1];
+    hit = hit || (ra <= rc && ra <= yb && rc >= ya);
+  }
+  return hit;
+}
+
 // Step 2: the two segment tables from the rows table (thread per 128-wide block).
 __global__ __launch_bounds__(256) void corr_window_segments_kernel(const int* __restrict__ rows, int H, int W, PyrLayout P,
                                                                     int nbA, int nbB, int* __restrict__ segA,
@@ -551,50 +633,169 @@ __global__ __launch_bounds__(256) void corr_window_segments_kernel(const int* __
   const int b = blockIdx.y, Q = H * W;
   const int* s_rows = rows + (long long)b * P.L * H * 2;   // [L][H][2]
   const int j0 = blockIdx.x * blockDim.x + threadIdx.x;
-  // table A: query block j = queries [128 j, 128 j + 127] = query rows qa..qb
-  if (j0 < nbA) {
-    const int j = j0;
-    const int qa = (j * BN) / W, qb = min((j * BN + BN - 1) / W, H - 1);
-    int* o = segA + ((long long)b * nbA + j) * SEG_INTS;
-    int n = 0;
-    for (int l = 0; l < P.L; ++l) {
-      int ylo = 1 << 30, yhi = -1;
-      for (int qy = qa; qy <= qb; ++qy) {
-        const int a = s_rows[(l * H + qy) * 2], c = s_rows[(l * H + qy) * 2 + 1];
-        if (a <= c) { ylo = min(ylo, a); yhi = max(yhi, c); }
-      }
-      if (ylo <= yhi) {
-        const int beg = P.off[l] + (ylo >> 2) * P.tw[l] * 16, end = P.off[l] + ((yhi >> 2) + 1) * P.tw[l] * 16;
-        if (n > 0 && o[2 * n] == beg) o[2 * n] = end;           // adjacent to the previous segment: merge
-        else { o[1 + 2 * n] = beg; o[2 + 2 * n] = end; ++n; }
-      }
-    }
-    o[0] = n;
-    for (int i = n; i < 4; ++i) { o[1 + 2 * i] = 0; o[2 + 2 * i] = 0; }
-    o[9] = 0;
-  }
+  if (j0 < nbA) window_record_a(s_rows, j0, H, W, P, segA + ((long long)b * nbA + j0) * SEG_INTS);
   // table B: column block j = slab columns [128 j, 128 j + 127]: hull of the query rows that reach any of its tile rows
   if (j0 >= nbA && j0 < nbA + nbB) {
     const int j = j0 - nbA;
     const int ca = j * BN, cb = min(j * BN + BN, P.slab) - 1;
     int qlo = 1 << 30, qhi = -1;
-    for (int l = 0; l < P.L; ++l) {
-      const int lbeg = P.off[l], lend = (l + 1 < P.L ? P.off[l + 1] : P.zero) - 1;
-      const int a = max(ca, lbeg), c = min(cb, lend);
-      if (a > c) continue;
-      const int ya = ((a - lbeg) / (P.tw[l] * 16)) * 4, yb = ((c - lbeg) / (P.tw[l] * 16)) * 4 + 3;   // texel rows
-      for (int qy = 0; qy < H; ++qy) {
-        const int ra = s_rows[(l * H + qy) * 2], rc = s_rows[(l * H + qy) * 2 + 1];
-        if (ra <= rc && ra <= yb && rc >= ya) { qlo = min(qlo, qy); qhi = max(qhi, qy); }
-      }
-    }
+    for (int qy = 0; qy < H; ++qy)
+      if (window_row_reaches(s_rows, qy, ca, cb, H, P)) { qlo = min(qlo, qy); qhi = max(qhi, qy); }
     int* o = segB + ((long long)b * nbB + j) * SEG_INTS;
-    for (int i = 0; i < SEG_INTS; ++i) o[i] = 0;
-    if (qlo <= qhi) {
-      o[0] = 1;
-      o[1] = (qlo * W) / BK * BK;
-      o[2] = min(((qhi + 1) * W + BK - 1) / BK * BK, (Q + BK - 1) / BK * BK);
+    o[0] = qlo <= qhi ? 1 : 0;
+    o[1] = 2;   // (one hull: the run tables' last widening)
+    o[2] = o[4] = qlo <= qhi ? (qlo * W) / BK * BK : 0;
+    o[3] = o[5] = qlo <= qhi ? min(((qhi + 1) * W + BK - 1) / BK * BK, (Q + BK - 1) / BK * BK) : 0;
+  }
+}
+
+// ---- df2ext's table with the windows clipped in x as well (W % RUN == 0, H <= RUNS_MAX_H) ----
+// Step 1: one workgroup per (batch item, query row): the rows table as above and, per run of RUN consecutive queries, the
+// min / max of cx and of cy over all lookups -> per level the texels (xlo, xhi, ylo, yhi) the run's windows can have
+// touched (runs table [B][L][H][W / RUN][4]; a range may come out empty).  A NaN coordinate in a run: the run reaches
+// everything.
+__global__ __launch_bounds__(256) void corr_window_runs_kernel(CoordList cl, int H, int W, int r, PyrLayout P,
+                                                                int* __restrict__ rows, int* __restrict__ runs) {
+  __shared__ float s_lo[4], s_hi[4];
+  const int b = blockIdx.y, qy = blockIdx.x, Q = H * W, NR = W / RUN;
+  float rlo = 3.0e38f, rhi = -3.0e38f;   // the row's cy, as corr_window_rows_kernel
+  bool rbad = false;
+  for (int x0 = 0; x0 < W; x0 += 256) {
+    const int x = x0 + threadIdx.x;
+    float xlo = 3.0e38f, xhi = -3.0e38f, ylo = 3.0e38f, yhi = -3.0e38f;
+    bool bad = false;
+    if (x < W)
+      for (int i = 0; i < cl.n; ++i) {
+        const float* c = cl.p[i] + (long long)b * 2 * Q + (long long)qy * W + x;
+        const float vx = c[0], vy = c[Q];
+        bad = bad || !(vx == vx) || !(vy == vy);
+        rbad = rbad || !(vy == vy);
+        xlo = fminf(xlo, vx);
+        xhi = fmaxf(xhi, vx);
+        ylo = fminf(ylo, vy);
+        yhi = fmaxf(yhi, vy);
+      }
+    rlo = fminf(rlo, ylo);
+    rhi = fmaxf(rhi, yhi);
+#pragma unroll
+    for (int o = RUN / 2; o > 0; o >>= 1) {   // (runs are aligned groups of RUN lanes: W % RUN == 0)
+      xlo = fminf(xlo, __shfl_xor(xlo, o, 64));
+      xhi = fmaxf(xhi, __shfl_xor(xhi, o, 64));
+      ylo = fminf(ylo, __shfl_xor(ylo, o, 64));
+      yhi = fmaxf(yhi, __shfl_xor(yhi, o, 64));
+      bad = __shfl_xor((int)bad, o, 64) != 0 || bad;
     }
+    if (bad) { xlo = ylo = -3.0e38f; xhi = yhi = 3.0e38f; }
+    if (x < W && x % RUN == 0)
+      for (int l = 0; l < P.L; ++l) {
+        const float inv = 1.0f / (float)(1 << l);
+        const auto tex = [&](float v) { return (int)fminf(fmaxf(floorf(v * inv), -1.0e8f), 1.0e8f); };
+        int4 t;
+        t.x = max(tex(xlo) - r - 1, 0);
+        t.y = min(tex(xhi) + r + 2, P.w[l] - 1);
+        t.z = max(tex(ylo) - r - 1, 0);
+        t.w = min(tex(yhi) + r + 2, P.h[l] - 1);
+        *reinterpret_cast<int4*>(runs + ((((long long)b * P.L + l) * H + qy) * NR + x / RUN) * 4) = t;
+      }
+  }
+  if (__syncthreads_or(rbad)) { rlo = -3.0e38f; rhi = 3.0e38f; }   // NaN cy in the row: assume every row
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    rlo = fminf(rlo, __shfl_xor(rlo, o, 64));
+    rhi = fmaxf(rhi, __shfl_xor(rhi, o, 64));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    s_lo[threadIdx.x >> 6] = rlo;
+    s_hi[threadIdx.x >> 6] = rhi;
+  }
+  __syncthreads();
+  if (threadIdx.x < P.L) {
+    const int l = threadIdx.x;
+    rlo = fminf(fminf(s_lo[0], s_lo[1]), fminf(s_lo[2], s_lo[3]));
+    rhi = fmaxf(fmaxf(s_hi[0], s_hi[1]), fmaxf(s_hi[2], s_hi[3]));
+    const float inv = 1.0f / (float)(1 << l);
+    const float flo = fminf(fmaxf(floorf(rlo * inv), -1.0e8f), 1.0e8f), fhi = fminf(fmaxf(floorf(rhi * inv), -1.0e8f), 1.0e8f);
+    int* o = rows + (((long long)b * P.L + l) * H + qy) * 2;
+    o[0] = max((int)flo - r - 1, 0);
+    o[1] = min((int)fhi + r + 2, P.h[l] - 1);
+  }
+}
+
+// Step 2: one wave per record.
+//   segA[b][query block j]: as corr_window_segments_kernel (a block is 128 consecutive queries, a whole feature row at
+//     W = 128: its windows span the width, there is nothing to clip in x).
+//   segB[b][column block j]: the hull as corr_window_segments_kernel; inside it, per query row, the hull of the runs whose
+//     windows reach the block's tiles, one segment [qy W + RUN run_lo, qy W + RUN (run_hi + 1)) each.  More than SEG_CAP:
+//     whole query rows, then the hull itself.  Adjacent segments are merged; a widening never drops a texel a window
+//     can touch.
+constexpr int RUNS_MAX_H = 1024;   // (the reach of a block's query rows is staged in LDS)
+__global__ __launch_bounds__(64) void corr_window_run_segments_kernel(const int* __restrict__ rows,
+                                                                       const int* __restrict__ runs, int H, int W,
+                                                                       PyrLayout P, int nbA, int nbB,
+                                                                       int* __restrict__ segA, int* __restrict__ segB) {
+  __shared__ short s_lo[RUNS_MAX_H], s_hi[RUNS_MAX_H];
+  const int b = blockIdx.y, NR = W / RUN, lane = threadIdx.x, Q = H * W;
+  const int* s_rows = rows + (long long)b * P.L * H * 2;                                     // [L][H][2]
+  const int4* s_runs = reinterpret_cast<const int4*>(runs) + (long long)b * P.L * H * NR;   // [L][H][NR]
+  if ((int)blockIdx.x < nbA) {
+    if (lane == 0) window_record_a(s_rows, blockIdx.x, H, W, P, segA + ((long long)b * nbA + blockIdx.x) * SEG_INTS);
+    return;
+  }
+  const int j = blockIdx.x - nbA;
+  if (j >= nbB) return;
+  // the block's tiles, per level: a rectangle of texels (a block inside one tile row: its tiles; else whole tile rows)
+  const int ca = j * BN, cb = min(j * BN + BN, P.slab) - 1;
+  for (int qy = lane; qy < H; qy += 64) {
+    int lo = NR, hi = -1;
+    const bool in_hull = window_row_reaches(s_rows, qy, ca, cb, H, P);   // (outside the hull nothing is walked)
+    if (in_hull)
+      for (int l = 0; l < P.L; ++l) {
+        const int lbeg = P.off[l], lend = (l + 1 < P.L ? P.off[l + 1] : P.zero) - 1;
+        const int a = max(ca, lbeg), c = min(cb, lend);
+        if (a > c) continue;
+        const int ta = (a - lbeg) >> 4, tb = (c - lbeg) >> 4, tya = ta / P.tw[l], tyb = tb / P.tw[l];
+        const int txa = tya == tyb ? ta - tya * P.tw[l] : 0, txb = tya == tyb ? tb - tyb * P.tw[l] : P.tw[l] - 1;
+        for (int rx = 0; rx < NR; ++rx) {
+          const int4 v = s_runs[((long long)l * H + qy) * NR + rx];
+          if (v.x <= v.y && v.z <= v.w && v.x <= txb * 4 + 3 && v.y >= txa * 4 && v.z <= tyb * 4 + 3 && v.w >= tya * 4) {
+            lo = min(lo, rx);
+            hi = max(hi, rx);
+          }
+        }
+      }
+    s_lo[qy] = (short)lo;
+    s_hi[qy] = (short)(in_hull ? hi : -2);   // -1: no run reaches ; -2: not among the hull's rows
+  }
+  __syncthreads();
+  if (lane == 0) {
+    int* o = segB + ((long long)b * nbB + j) * SEG_INTS;
+    int qlo = 1 << 30, qhi = -1;
+    for (int qy = 0; qy < H; ++qy)
+      if (s_hi[qy] != -2) { qlo = min(qlo, qy); qhi = max(qhi, qy); }
+    o[2] = qlo <= qhi ? (qlo * W) / BK * BK : 0;
+    o[3] = qlo <= qhi ? min(((qhi + 1) * W + BK - 1) / BK * BK, (Q + BK - 1) / BK * BK) : 0;
+    int n = 0, mode = 0;
+    for (; mode < 3; ++mode) {   // 0: the runs' hull per query row ; 1: whole query rows ; 2: the hull
+      n = 0;
+      int last = -1;
+      bool fits = true;
+      for (int qy = 0; qy < H; ++qy) {
+        if (s_hi[qy] < 0) continue;
+        const int beg = qy * W + (mode == 0 ? RUN * s_lo[qy] : 0), end = qy * W + (mode == 0 ? RUN * (s_hi[qy] + 1) : W);
+        if (n > 0 && (last == beg || mode == 2)) {
+          o[3 + 2 * n] = end;
+        } else {
+          if (n == SEG_CAP) { fits = false; break; }
+          o[4 + 2 * n] = beg;
+          o[5 + 2 * n] = end;
+          ++n;
+        }
+        last = end;
+      }
+      if (fits) break;
+    }
+    o[0] = n;
+    o[1] = mode;
   }
 }
 
@@ -697,12 +898,43 @@ extern "C" int pcfa_corr_pyramid_bwd(const float* dpyr, const float* fmap1, cons
                      nullptr, nullptr);
 }
 
+// Shape of the segment tables behind the split-K area of the windows workspace.  runs: df2ext's lists are clipped in x as
+// well (the runs table); else both tables come from the rows table alone (W % RUN != 0, very tall maps).
+struct WindowTables {
+  bool runs;
+  int nbA, nbB;          // records of table A (blocks of dfmap1's queries) / table B (blocks of df2ext's slab columns)
+  size_t rows_off;       // ints from the start of table A to the rows table, then (16-B aligned) the runs table
+  size_t runs_off;
+  size_t ints;
+};
+static WindowTables window_tables(int B, int H, int W, const PyrLayout& P) {
+  WindowTables t;
+  t.runs = W % RUN == 0 && H <= RUNS_MAX_H && P.L <= 4;
+  t.nbA = pcfa_cdiv((long long)H * W, BN);
+  t.nbB = pcfa_cdiv(P.slab, BN);
+  t.rows_off = (size_t)SEG_INTS * B * (t.nbA + t.nbB);
+  t.runs_off = (t.rows_off + 2 * (size_t)B * P.L * H + 3) & ~(size_t)3;
+  t.ints = t.runs_off + (t.runs ? 4 * (size_t)B * P.L * H * (W / RUN) : 0);
+  return t;
+}
+
 extern "C" size_t pcfa_corr_pyramid_bwd_windows_workspace_bytes(int B, int D, int H, int W, int num_levels) {
   PyrLayout P;
   const size_t base = pcfa_corr_pyramid_bwd_workspace_bytes(B, D, H, W, num_levels);
   if (base == 0 || !pcfa_make_layout(P, H, W, num_levels)) return 0;
-  const size_t nbA = (size_t)pcfa_cdiv((long long)H * W, BN), nbB = (size_t)pcfa_cdiv(P.slab, BN);
-  return ((base + 15) & ~(size_t)15) + sizeof(int) * (SEG_INTS * B * (nbA + nbB) + 2 * (size_t)B * P.L * H);
+  return ((base + 15) & ~(size_t)15) + sizeof(int) * window_tables(B, H, W, P).ints;
+}
+
+extern "C" int pcfa_corr_pyramid_bwd_windows_tables(int H, int W, int num_levels, int* out) {
+  PyrLayout P;
+  if (!out || !pcfa_make_layout(P, H, W, num_levels)) return PCFA_ERR_INVALID_ARG;
+  const WindowTables t = window_tables(1, H, W, P);
+  out[0] = SEG_INTS;
+  out[1] = t.nbA;
+  out[2] = t.nbB;
+  out[3] = t.runs ? RUN : 0;
+  out[4] = SEG_CAP;
+  return PCFA_OK;
 }
 
 extern "C" int pcfa_corr_pyramid_bwd_windows(const float* dpyr, const float* fmap1, const float* f2ext, float* dfmap1,
@@ -719,9 +951,10 @@ extern "C" int pcfa_corr_pyramid_bwd_windows(const float* dpyr, const float* fma
   // (a segment record holds four levels' ranges: deeper pyramids take the dense products)
   if (!coords || n_coords < 1 || n_coords > MAX_COORDS || !fast || H > 65535 || num_levels > 4)   // no window information:
     return pyramid_bwd(dpyr, fmap1, f2ext, dfmap1, dfmap2, workspace, workspace_bytes, B, D, H, W, num_levels, stream,
-                       nullptr, nullptr);                                                   // the dense products
+                       nullptr, nullptr);                                            // the dense products
   if (workspace_bytes < pcfa_corr_pyramid_bwd_windows_workspace_bytes(B, D, H, W, num_levels)) return PCFA_ERR_WORKSPACE;
-  const int nbA = pcfa_cdiv(Q, BN), nbB = pcfa_cdiv(P.slab, BN);
+  const WindowTables t = window_tables(B, H, W, P);
+  const int nbA = t.nbA, nbB = t.nbB;
   int* segA = reinterpret_cast<int*>((char*)workspace + base);
   int* segB = segA + (size_t)SEG_INTS * B * nbA;
   CoordList cl;
@@ -729,11 +962,19 @@ extern "C" int pcfa_corr_pyramid_bwd_windows(const float* dpyr, const float* fma
   for (int i = 0; i < MAX_COORDS; ++i) cl.p[i] = i < n_coords ? coords[i] : nullptr;
   for (int i = 0; i < n_coords; ++i)
     if (!cl.p[i]) return PCFA_ERR_INVALID_ARG;
-  int* rows = segB + (size_t)SEG_INTS * B * nbB;
-  pcfa_launch(corr_window_rows_kernel, dim3(H, B), dim3(256), 0, (hipStream_t)stream, cl, H, W, radius, P, rows);
-  PCFA_LAUNCH_CHECK();
-  pcfa_launch(corr_window_segments_kernel, dim3(pcfa_cdiv(nbA + nbB, 256), B), dim3(256), 0, (hipStream_t)stream,
-              (const int*)rows, H, W, P, nbA, nbB, segA, segB);
+  int* rows = segA + t.rows_off;
+  int* runs = segA + t.runs_off;
+  if (t.runs) {
+    pcfa_launch(corr_window_runs_kernel, dim3(H, B), dim3(256), 0, (hipStream_t)stream, cl, H, W, radius, P, rows, runs);
+    PCFA_LAUNCH_CHECK();
+    pcfa_launch(corr_window_run_segments_kernel, dim3(nbA + nbB, B), dim3(64), 0, (hipStream_t)stream, (const int*)rows,
+                (const int*)runs, H, W, P, nbA, nbB, segA, segB);
+  } else {
+    pcfa_launch(corr_window_rows_kernel, dim3(H, B), dim3(256), 0, (hipStream_t)stream, cl, H, W, radius, P, rows);
+    PCFA_LAUNCH_CHECK();
+    pcfa_launch(corr_window_segments_kernel, dim3(pcfa_cdiv(nbA + nbB, 256), B), dim3(256), 0, (hipStream_t)stream,
+                (const int*)rows, H, W, P, nbA, nbB, segA, segB);
+  }
   PCFA_LAUNCH_CHECK();
   return pyramid_bwd(dpyr, fmap1, f2ext, dfmap1, dfmap2, workspace, base, B, D, H, W, num_levels, stream, segA, segB);
 }

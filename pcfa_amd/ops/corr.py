@@ -57,7 +57,7 @@ class _CorrBuild(torch.autograd.Function):
         df1 = torch.empty_like(f1)
         df2 = torch.empty_like(f1)
         # the coordinates of every lookup that accumulated into dpyr: the products skip what no window touched
-        # (the per-block segment record of corr_window_segments_kernel holds four levels: more levels -> dense products)
+        # (the segment tables of csrc/corr_pyramid.hip are built for up to four levels: more levels -> dense products)
         cs = st.coords_bwd if (st.coords_bwd and len(st.coords_bwd) <= 32 and st.bwd_windows and st.L <= 4) else []
         if cs:
             nbytes = lib.pcfa_corr_pyramid_bwd_windows_workspace_bytes(B, D, H, W, st.L)
@@ -67,13 +67,11 @@ class _CorrBuild(torch.autograd.Function):
                   ctypes.c_size_t(nbytes), ptrs, len(cs), st.r, B, D, H, W, st.L)
             if core.work_recorder() is not None:
                 # executed matrix work of the two sparse products: the K segments the kernels walked, read back from the
-                # workspace (csrc/corr_pyramid.hip: per 128-wide column block {count, (begin, end) x 4, pad} ints behind
-                # the split-K area; segA = blocks of dfmap1's Q columns, segB = blocks of df2ext's slab columns)
-                base = (int(lib.pcfa_corr_pyramid_bwd_workspace_bytes(B, D, H, W, st.L)) + 15) & ~15
-                nbA, nbB = -(-(H * W) // 128), -(-st.slab // 128)
-                seg = ws.view(torch.int32)[base // 4: base // 4 + 10 * B * (nbA + nbB)].cpu().view(-1, 10).long()
-                live = torch.arange(4)[None, :] < seg[:, :1]
-                k = ((seg[:, 2:9:2] - seg[:, 1:8:2]) * live).sum(1)
+                # workspace (pcfa_corr_pyramid_bwd_windows_tables: per block {count, widening, hull, (begin, end) x capacity}
+                # ints behind the split-K area; segA = blocks of dfmap1's queries, segB = blocks of df2ext's slab columns)
+                seg, nbA, _ = window_segment_tables(ws, B, D, H, W, st.L)
+                live = torch.arange((seg.shape[1] - 4) // 2)[None, :] < seg[:, :1]
+                k = ((seg[:, 5::2] - seg[:, 4::2]) * live).sum(1)
                 dense = 2.0 * B * D * (H * W) ** 2
                 _note_work("corr_pyramid_gemm_dfmap1", dense, 2.0 * D * 128 * float(k[:B * nbA].sum()))
                 _note_work("corr_pyramid_gemm_df2ext", dense, 2.0 * D * 128 * float(k[B * nbA:].sum()))
@@ -86,6 +84,19 @@ class _CorrBuild(torch.autograd.Function):
         st.token_grad = None
         st.coords_bwd = None
         return df1, df2, None
+
+
+def window_segment_tables(ws, B, D, H, W, L):
+    """The K-segment records pcfa_corr_pyramid_bwd_windows left in its workspace `ws`, on the host: (int64 records
+    [B * (nbA + nbB)][ints per record], table A first, then table B; nbA; pcfa_corr_pyramid_bwd_windows_tables's row)."""
+    lib = _hip.load()
+    info = (ctypes.c_int * 8)()
+    if lib.pcfa_corr_pyramid_bwd_windows_tables(H, W, L, info) != 0:
+        raise ValueError("no pyramid layout for %dx%d, %d levels" % (H, W, L))
+    rec, nbA, nbB = info[0], info[1], info[2]
+    base = (int(lib.pcfa_corr_pyramid_bwd_workspace_bytes(B, D, H, W, L)) + 15) & ~15
+    seg = ws.view(torch.int32)[base // 4: base // 4 + rec * B * (nbA + nbB)].cpu().view(-1, rec).long()
+    return seg, nbA, list(info)
 
 
 def _token_grad(st, device):
