@@ -15,13 +15,11 @@ computed inside the forward graph and collected in a device buffer that is read 
 in `step()` allocates or waits for the GPU, so several pairs can be in flight (attack_PCFA.PairsInFlight)."""
 import os
 import time
-import weakref
 
 import torch
 
-from . import config, ops, sharding
-from .attack_PCFA import (PairsInFlight, _graphs_enabled, _hardware_queues_for, _load_model, _log_eviction, _should_save,
-                          select_device)
+from . import config, graph_sets, ops, sharding
+from .attack_PCFA import PairsInFlight, _graphs_enabled, _hardware_queues_for, _load_model, _should_save, select_device
 from .helper_functions import datasets, logging, losses, ownutilities, parsing_file, targets
 
 # columns of the per-iteration history, under the reference's metric names (attack_FGSM.py:234-241)
@@ -41,51 +39,6 @@ def fgsm_attack_step(image1, image2, epsilon, image1_grad, image2_grad, image_mi
         p1 = torch.clamp(p1, image_min, image_max)
         p2 = torch.clamp(p2, image_min, image_max)
     return p1, p2
-
-
-class _FgsmGraphs:
-    """What one pair leaves to the next pair of the same key: the static buffers the two graphs read and write, and the
-    graphs (the counterpart of attack_PCFA._PairGraphs; there is no optimiser state in I-FGSM)."""
-
-    def __init__(self, st):
-        self.x1, self.x2, self.image1, self.image2 = st.x1, st.x2, st.image1, st.image2
-        self.d1, self.d2 = st.delta1, st.delta2
-        self.target, self.flow_init, self.flow_gt_buf = st.target, st.flow_pred_init, st._flow_gt_buf
-        self.graphed = st.graphed
-        self.captures = 1          # how often this set was captured: stays 1 however many pairs adopt it
-        self.pairs = 1
-        self.owner = weakref.ref(st)   # the ONE live FgsmAttack of this key
-
-    def retire_owner(self):
-        st = self.owner()
-        if st is not None:
-            st._retire()
-
-
-def _fgsm_graph_cache(model):
-    """key -> _FgsmGraphs, least recently used first.  A cache of its own: PCFA's (`_pcfa_pair_graphs`) and its cap are not
-    touched by this attack."""
-    cache = getattr(model, "_pcfa_fgsm_graphs", None)
-    if cache is None:
-        cache = {}
-        try:
-            object.__setattr__(model, "_pcfa_fgsm_graphs", cache)   # plain attribute: not a module / parameter
-        except Exception:  # noqa: BLE001
-            return {}
-    return cache
-
-
-def _fgsm_cache_put(cache, key, kept, cap):
-    """Insert `kept` as the most recently used set; the cap counts the sets of `key`'s LANE only (the last element of a key),
-    so that a lane's new shape can only evict an older shape of the same lane -- never the live set of another lane."""
-    cache.pop(key, None)
-    cache[key] = kept
-    mine = [k for k in cache if k[-1] == key[-1]]      # dicts keep insertion order: oldest first
-    for old_key in mine[:max(0, len(mine) - max(1, int(cap)))]:
-        old = cache.pop(old_key)
-        _log_eviction("fgsm-graph", old_key)
-        old.retire_owner()                 # its FgsmAttack must not replay graphs whose buffers are about to go
-        old.graphed = None
 
 
 class FgsmAttack:
@@ -127,31 +80,23 @@ class FgsmAttack:
         self.step_launches = 0
         self._hist = None          # device buffer [steps][6]: one row of metrics per iteration
         self._history = []         # the rows read back so far, as dicts
-        kept = _fgsm_graph_cache(model).get(self.graph_key) if (use_graph and reuse_graphs) else None
+        # same key as an earlier pair: its static buffers and graphs (KEPT), refilled.  The earlier FgsmAttack (if still alive)
+        # is retired first -- it keeps copies of its results.
+        kept = graph_sets.adopt(self._graph_sets(), self.graph_key, self) if (use_graph and reuse_graphs) else None
         self.graphs_reused = kept is not None
 
         if kept is not None:
-            # same key as an earlier pair: its static buffers and graphs, refilled.  The earlier FgsmAttack (if still alive)
-            # is retired first -- it keeps copies of its results.
-            kept.retire_owner()
-            kept.owner = weakref.ref(self)
-            _fgsm_cache_put(_fgsm_graph_cache(model), self.graph_key, kept, config.cfg(model).max_cached_shapes)
             with torch.no_grad():
-                kept.image1.copy_(image1)
-                kept.image2.copy_(image2)
-                kept.x1.copy_(image1)
-                kept.x2.copy_(image2)
-                kept.d1.zero_()
-                kept.d2.zero_()
+                self.image1.copy_(image1)
+                self.image2.copy_(image2)
+                self.x1.copy_(image1)
+                self.x2.copy_(image2)
+                self.delta1.zero_()
+                self.delta2.zero_()
                 if self.flow_gt is not None:
-                    kept.flow_gt_buf.copy_(self.flow_gt)
+                    self._flow_gt_buf.copy_(self.flow_gt)
                 else:
-                    kept.flow_gt_buf.zero_()
-            self.image1, self.image2, self.x1, self.x2 = kept.image1, kept.image2, kept.x1, kept.x2
-            self.delta1, self.delta2 = kept.d1, kept.d2
-            self.target, self.flow_pred_init, self._flow_gt_buf = kept.target, kept.flow_init, kept.flow_gt_buf
-            self.graphed = kept.graphed
-            kept.pairs += 1
+                    self._flow_gt_buf.zero_()
             self._begin_graphed()
         else:
             self.image1, self.image2 = image1.detach(), image2.detach()
@@ -171,6 +116,13 @@ class FgsmAttack:
         self.aee_tgt = logging.calc_metrics_const(self.target, self.flow_pred_init)
         logging.log_metrics(batch * args.steps, ("aee_pred-tgt", self.aee_tgt))
         self._hist = torch.empty((max(1, int(args.steps)), len(HISTORY_KEYS)), device=device, dtype=torch.float32)
+
+    # what one pair leaves to the next pair of the same key: the static buffers the two graphs read and write, and the graphs
+    # (there is no optimiser state in I-FGSM).  A cache of its own: PCFA's (`_pcfa_pair_graphs`) is not touched by this attack
+    KEPT = ("x1", "x2", "image1", "image2", "delta1", "delta2", "target", "flow_pred_init", "_flow_gt_buf", "graphed")
+
+    def _graph_sets(self):
+        return graph_sets.cache(self.model, "fgsm-graph")
 
     # ---- pieces of one iteration --------------------------------------------------------------------------------
     def predict(self):
@@ -204,14 +156,14 @@ class FgsmAttack:
             self._flow_gt_buf = self.flow_gt.clone() if self.flow_gt is not None else torch.zeros_like(flow0)
             # the step kernel is launched OUTSIDE the captured graphs: warm-up and capture leave the images where they are
             self.graphed = SplitGraphedStep(self._forward_with_metrics, self._loss, [self.x1, self.x2])
-            if self.reuse_graphs:
-                _fgsm_cache_put(_fgsm_graph_cache(self.model), self.graph_key, _FgsmGraphs(self),
-                                config.cfg(self.model).max_cached_shapes)   # the next pair of this key adopts them
+            if self.reuse_graphs:   # the next pair of this key adopts them
+                graph_sets.put(self._graph_sets(), self.graph_key, graph_sets.GraphSet(self, self.graph_key[-1], self.KEPT),
+                               config.cfg(self.model).max_cached_shapes, "fgsm-graph")
             self._begin_graphed()
         except Exception as e:  # noqa: BLE001 -- the eager loop launches the same kernels in the same order
             import logging as pylog
             pylog.warning("hipGraph capture of the I-FGSM iteration failed (%r): launching eagerly", e)
-            _fgsm_graph_cache(self.model).pop(self.graph_key, None)
+            self._graph_sets().pop(self.graph_key, None)
             self.graphed = None
             self.x1.grad = self.x2.grad = None
 

@@ -21,13 +21,13 @@ is data parallel over the batch with ONE all-reduce of d(loss)/d(delta) per clos
 (`attack_l2_universal`), see pcfa_amd/sharding.py.
 """
 import os
-import weakref
 import time
 
 import numpy as np
 import torch
 
-from . import _hip, config, ops, sharding
+from . import _hip, config, graph_sets, ops, sharding
+from .graph_sets import _log_eviction
 from .helper_functions import datasets, logging, losses, ownutilities, parsing_file, targets
 from .helper_functions.config_paths import Conf
 
@@ -69,9 +69,9 @@ def _should_save(batch, args):
 
 
 def best_iterate_rule(below_threshold, l2_delta12, aee_adv_tgt, delta12_min, aee_adv_tgt_min, delta_bound):
-    """The best-iterate rule (attack_PCFA.py:226-243), stated once for PairAttack.step and PairBatch.step: until an iterate
-    has met the bound the smallest perturbation wins (ties: the smaller AEE to the target); from then on the smallest AEE
-    to the target among the iterates inside the bound.  Returns (record this iterate, an iterate has met the bound)."""
+    """The best-iterate rule (attack_PCFA.py:226-243): until an iterate has met the bound the smallest perturbation wins
+    (ties: the smaller AEE to the target); from then on the smallest AEE to the target among the iterates inside the bound.
+    Returns (record this iterate, an iterate has met the bound)."""
     if below_threshold:
         return l2_delta12 <= delta_bound and aee_adv_tgt < aee_adv_tgt_min, True
     if l2_delta12 < delta12_min or (l2_delta12 == delta12_min and aee_adv_tgt < aee_adv_tgt_min):
@@ -83,391 +83,15 @@ def _graphs_enabled(device, args):
     return torch.device(device).type == "cuda" and os.environ.get("PCFA_HIP_GRAPH", "1") == "1" and args.steps > 0
 
 
-class _PairGraphs:
-    """What survives from one image pair to the next of the same shape and flags (attack_PCFA.py:668-670 loops over
-    a batch-1 loader: every KITTI / Sintel pair has the same size): the static device buffers the captured closure
-    reads and writes, the hipGraphs themselves and the optimiser whose flat gradient buffer the closure fills.  A new
-    pair copies its images / initial variables / target into these buffers and resets the optimiser -- no warm-up, no
-    re-capture (`PairAttack(..., reuse_graphs=True)`, the default on the GPU; results equal a fresh capture:
-    tests/test_gpu_parity.py::test_pair_graph_reuse_equals_fresh_capture)."""
-
-    def __init__(self, st):
-        self.image1, self.image2 = st.image1, st.image2
-        self.images_max, self.images_min = st.images_max, st.images_min
-        self.params, self.target, self.optimizer = st.params, st.target, st.optimizer
-        self.graphed, self.repredict = st.graphed, st.repredict
-        self.pairs = 1
-        self.owner = weakref.ref(st)   # the ONE live PairAttack of this key; retired when the next pair adopts the set
-
-    def retire_owner(self):
-        st = self.owner()
-        if st is not None:
-            st._retire()
-
-
 def _max_cached_shapes(model):
-    """Graph sets kept per model (LRU), from the model's Config (default 4; KITTI under /8 padding alone has three padded
-    shapes).  Each set pins a closure graph pool + a 2 x 101 x n L-BFGS history (~1.1 GB at 440x1024)."""
+    """Graph sets kept per model and lane (graph_sets.put) and batch states per universal attack, from the model's Config
+    (default 4; KITTI under /8 padding alone has three padded shapes)."""
     return config.cfg(model).max_cached_shapes
 
 
-def _log_eviction(what, key):
-    import logging as pylog
-    pylog.warning("pcfa_amd: %s cache full: dropping the graph set of %r -- the next pair of that shape pays warm-up + "
-                  "capture again (raise Config.max_cached_shapes / PCFA_MAX_CACHED_SHAPES if this repeats)", what, key)
-
-
-def _cache_put(cache, key, kept, cap):
-    cache.pop(key, None)
-    cache[key] = kept                      # dicts keep insertion order: the last entry is the most recently used
-    while len(cache) > cap:
-        old_key = next(iter(cache))
-        old = cache.pop(old_key)
-        _log_eviction("pair-graph", old_key)
-        old.retire_owner()                 # its PairAttack must not replay graphs whose buffers are about to go
-        old.graphed = old.repredict = old.optimizer = None
-
-
-def _graph_cache(model):
-    cache = getattr(model, "_pcfa_pair_graphs", None)
-    if cache is None:
-        cache = {}
-        try:
-            object.__setattr__(model, "_pcfa_pair_graphs", cache)   # plain attribute: not a module / parameter
-        except Exception:  # noqa: BLE001
-            return {}
-    return cache
-
-
-class PairAttack:
-    """Everything pcfa_attack holds for ONE image pair (attack_PCFA.py:40-247): the optimisation variables,
-    the optimiser, the target, the best-iterate bookkeeping -- and `step()`, the body of the `--steps` loop.
-
-    `pcfa_attack` is `PairAttack(...)` + `args.steps` x `step()`; bench.py times `step()` of this class, so the
-    measured loop IS the product loop.  On the GPU the closure (static shapes, variables updated in place by
-    L-BFGS) and the re-prediction forward are captured once per pair into hipGraphs and replayed
-    (`use_graph=None`: on for CUDA devices unless PCFA_HIP_GRAPH=0; if capture fails the eager closure -- the same
-    kernels in the same order -- is used and a warning is logged)."""
-
-    def __init__(self, model, image1, image2, flow, batch, eps_box, device, has_gt, optim_mu, args, use_graph=None,
-                 reuse_graphs=None):
-        self.model, self.args, self.device, self.batch = model, args, device, batch
-        if reuse_graphs is None:   # pairs of one shape share static buffers + hipGraphs unless the model's config says no
-            reuse_graphs = config.cfg(model).reuse_pair_graphs
-        self.has_gt, self.optim_mu, self.eps_box = has_gt, optim_mu, eps_box
-        curr_step = batch * args.steps
-
-        image1, image2 = image1.to(device), image2.to(device)
-        self.flow_gt = flow.to(device) if flow is not None else None
-        if not ownutilities.model_takes_unit_input(args.net):
-            image1 = image1 / 255.
-            image2 = image2 / 255.
-        self.padder, [image1, image2] = ownutilities.preprocess_img(args.net, image1, image2)
-        image1.requires_grad = False
-        image2.requires_grad = False
-        cov = args.boxconstraint in ['change_of_variables']
-        if args.joint_perturbation and cov:
-            raise ValueError("Training a --joint_perturbation with --boxconstraint=change_of_variables is not "
-                             "defined. Please use --boxconstraint=clipping.")
-        if use_graph is None:
-            use_graph = _graphs_enabled(device, args)
-        share_forward = os.environ.get("PCFA_SHARED_FORWARD", "0") == "1"
-        self.graph_key = (args.net, tuple(image1.shape), args.boxconstraint, bool(args.joint_perturbation), args.loss,
-                          float(optim_mu), float(args.delta_bound), float(eps_box), str(device), ops.core.current_lane())
-        kept = _graph_cache(model).get(self.graph_key) if (use_graph and reuse_graphs and not share_forward) else None
-        self.graphed = self.repredict = None
-        self.graphs_reused = kept is not None
-        self.retired = False
-
-        if kept is not None:
-            # same shape and flags as an earlier pair: its static buffers, graphs and optimiser, refilled.  The earlier
-            # PairAttack (if still alive) is retired first: its variables, target and optimiser state are this pair's now.
-            kept.retire_owner()
-            kept.owner = weakref.ref(self)
-            _cache_put(_graph_cache(model), self.graph_key, kept, _max_cached_shapes(model))   # most recently used
-            with torch.no_grad():
-                kept.image1.copy_(image1)
-                kept.image2.copy_(image2)
-                kept.images_max.copy_(torch.max(image1, image2))
-                kept.images_min.copy_(torch.min(image1, image2))
-                if args.joint_perturbation:
-                    kept.params[0].zero_()
-                elif cov:
-                    kept.params[0].copy_(torch.atanh(2. * (1. - eps_box) * image1 - (1 - eps_box)))
-                    kept.params[1].copy_(torch.atanh(2. * (1. - eps_box) * image2 - (1 - eps_box)))
-                else:
-                    kept.params[0].copy_(image1)
-                    kept.params[1].copy_(image2)
-            image1, image2 = kept.image1, kept.image2
-            self.image1, self.image2 = image1, image2
-            self.images_max, self.images_min = kept.images_max, kept.images_min
-            self.params = kept.params
-            for p_ in self.params:
-                p_.grad = None
-            kept.optimizer.reset()
-            self.optimizer = kept.optimizer
-            self.graphed, self.repredict = kept.graphed, kept.repredict
-            kept.pairs += 1
-            delta1 = torch.zeros_like(image1)
-            delta2 = torch.zeros_like(image2)
-            if args.joint_perturbation:
-                self.nw_delta = self.params[0]
-                self.nw_input1, self.nw_input2 = image1, image2
-                self.fwd_kwargs = {"delta1": self.nw_delta}
-            else:
-                self.nw_delta = None
-                self.nw_input1, self.nw_input2 = self.params
-                self.fwd_kwargs = {}
-            _, flow0 = self.repredict()           # the captured forward at the initial variables = unattacked flow
-            self.flow_pred_init = flow0.detach().clone()
-            target = targets.get_target(args.target, self.flow_pred_init,
-                                        custom_target_path=args.custom_target_path, device=device).to(device)
-            kept.target.copy_(target)
-            self.target = kept.target
-        else:
-            self.image1, self.image2 = image1, image2
-            self.images_max = torch.max(image1, image2).detach()
-            self.images_min = torch.min(image1, image2).detach()
-            delta1 = torch.zeros_like(image1)
-            delta2 = torch.zeros_like(image2)
-            self.nw_delta = None
-            if args.joint_perturbation:
-                self.nw_delta = delta1
-                self.nw_delta.requires_grad = True
-                self.nw_input1, self.nw_input2 = image1, image2
-                self.params = [self.nw_delta]
-                self.fwd_kwargs = {"delta1": self.nw_delta}
-            else:
-                if cov:
-                    self.nw_input1 = torch.atanh(2. * (1. - eps_box) * (image1 + delta1) - (1 - eps_box))
-                    self.nw_input2 = torch.atanh(2. * (1. - eps_box) * (image2 + delta2) - (1 - eps_box))
-                else:
-                    self.nw_input1 = image1 + delta1
-                    self.nw_input2 = image2 + delta2
-                self.nw_input1.requires_grad = True
-                self.nw_input2.requires_grad = True
-                self.params = [self.nw_input1, self.nw_input2]
-                self.fwd_kwargs = {}
-            self.optimizer = ops.get().LBFGS(self.params, max_iter=10)
-
-            with torch.no_grad():
-                self.flow_pred_init = self.predict().detach().clone()
-            self.target = targets.get_target(args.target, self.flow_pred_init,
-                                             custom_target_path=args.custom_target_path, device=device).to(device)
-        self.target.requires_grad = False
-
-        self.aee_tgt = logging.calc_metrics_const(self.target, self.flow_pred_init)
-        if has_gt:
-            self.aee_gt_tgt, self.aee_gt = logging.calc_metrics_const_gt(self.target, self.flow_pred_init,
-                                                                         self.flow_gt)
-        else:
-            self.aee_gt_tgt, self.aee_gt = None, None
-        logging.log_metrics(curr_step, ("aee_pred-tgt", self.aee_tgt), ("aee_gt-tgt", self.aee_gt_tgt),
-                            ("aee_pred-gt", self.aee_gt))
-        logging.log_metric(key="optim_mu", value=optim_mu, step=curr_step)
-
-        model.zero_grad()
-        self.optimizer.zero_grad()
-
-        self.delta_below_threshold = False
-        self.delta12_min_val = float('inf')
-        self.aee_adv_tgt_min_val = float('inf')
-        self.aee_adv_pred_min_val = 0.
-        self.delta1_min = self.delta2_min = self.flow_pred_min = None
-        self.flow_pred = self.flow_pred_init
-        self.delta1, self.delta2 = delta1, delta2
-        self.aee_adv_gt = 0.
-        self.aee_adv_tgt = self.aee_adv_pred = 0.
-        self.l2_delta1 = self.l2_delta2 = self.l2_delta12 = 0.
-        self.steps_done = 0
-        self.closures = 0
-
-        self.reuse_graphs = reuse_graphs
-        if use_graph and kept is None:
-            self.enable_graph()
-
-    # ---- pieces of the closure (attack_PCFA.py:175-192) ---------------------------------------------------------
-    def predict(self):
-        out = ownutilities.compute_flow(self.model, "scaled_input_model", self.nw_input1, self.nw_input2,
-                                        test_mode=True, **self.fwd_kwargs)
-        [out] = ownutilities.postprocess_flow(self.args.net, self.padder, out)
-        return out
-
-    def current_deltas(self):
-        if self.args.joint_perturbation:
-            return extract_deltas_joint(self.nw_delta, self.images_max, self.images_min)
-        return extract_deltas(self.nw_input1, self.nw_input2, self.image1, self.image2, self.args.boxconstraint,
-                              eps_box=self.eps_box)
-
-    def closure_body(self):
-        flow_closure = self.predict()
-        d1, d2 = self.current_deltas()
-        loss_closure = losses.loss_delta_constraint(flow_closure, self.target, d1, d2, self.device,
-                                                    delta_bound=self.args.delta_bound, mu=self.optim_mu,
-                                                    f_type=self.args.loss)
-        loss_closure.backward()
-        return loss_closure
-
-    def _repredict_body(self):
-        return self.current_deltas(), self.predict()
-
-    def _forward_with_loss(self):
-        """closure_body without the backward: (loss, ((delta1, delta2), flow)) -- see graphed.SplitGraphedClosure."""
-        flow = self.predict()
-        d1, d2 = self.current_deltas()
-        loss = losses.loss_delta_constraint(flow, self.target, d1, d2, self.device, delta_bound=self.args.delta_bound,
-                                            mu=self.optim_mu, f_type=self.args.loss)
-        return loss, ((d1, d2), flow)
-
-    def enable_graph(self, share_forward=None):
-        """share_forward (default: PCFA_SHARED_FORWARD=1, off otherwise): capture the closure as forward + backward graphs
-        and let the re-prediction after a step double as the forward of the next step's first closure evaluation."""
-        if share_forward is None:
-            share_forward = os.environ.get("PCFA_SHARED_FORWARD", "0") == "1"
-        try:
-            from .graphed import GraphedClosure, GraphedForward, SplitGraphedClosure
-            if share_forward:
-                split = SplitGraphedClosure(self._forward_with_loss, self.params)
-                self.graphed = split
-
-                def repredict():
-                    _, ((d1, d2), flow) = split.forward()
-                    return (d1.detach(), d2.detach()), flow.detach()
-                self.repredict = repredict
-                return
-            sink = getattr(self.optimizer, "flat_grad_views", None)
-            self.graphed = GraphedClosure(self.closure_body, self.params, grad_sink=sink() if sink else None)
-            self.repredict = GraphedForward(self._repredict_body, self.device)
-            if self.reuse_graphs and hasattr(self.optimizer, "reset"):
-                _cache_put(_graph_cache(self.model), self.graph_key, _PairGraphs(self),
-                           _max_cached_shapes(self.model))   # the next pair of this shape adopts them
-        except Exception as e:  # noqa: BLE001 -- the eager closure launches the same kernels in the same order
-            import logging as pylog
-            pylog.warning("hipGraph capture of the closure failed (%r): launching eagerly", e)
-            self.graphed = self.repredict = None
-
-    def _retire(self):
-        """A later pair of the same shape took over this pair's static buffers, graphs and optimiser (or the set was
-        evicted from the per-model cache): results recorded so far stay readable, further evaluation raises."""
-        self.retired = True
-        self.graphed = self.repredict = None
-
-    def _check_live(self):
-        if self.retired:
-            raise RuntimeError("this PairAttack was retired: a later pair of the same shape adopted its static buffers, "
-                               "graphs and optimiser (one live PairAttack per shape and model; reuse_graphs=False keeps "
-                               "pairs independent)")
-
-    def closure(self):
-        self._check_live()
-        self.closures += 1
-        if self.graphed is not None:
-            return self.graphed()
-        self.optimizer.zero_grad()
-        return self.closure_body()
-
-    # ---- one `--steps` iteration (attack_PCFA.py:155-247) -------------------------------------------------------
-    def step(self):
-        self._check_live()
-        args = self.args
-        steps = self.steps_done
-        curr_step = self.batch * args.steps + steps
-        logging.log_metrics(curr_step, ("batch", self.batch), ("steps", steps), ("epoch", 0))
-
-        self.optimizer.step(self.closure)
-
-        if self.repredict is not None:
-            (delta1, delta2), flow_pred = self.repredict()
-        else:
-            with torch.no_grad():
-                (delta1, delta2), flow_pred = self._repredict_body()
-        self.delta1, self.delta2, self.flow_pred = delta1, delta2, flow_pred
-
-        aee_adv_tgt, aee_adv_pred = logging.calc_metrics_adv(flow_pred, self.target, self.flow_pred_init)
-        self.aee_adv_gt = logging.calc_metrics_adv_gt(flow_pred, self.flow_gt) if self.has_gt else None
-        logging.log_metrics(curr_step, ("aee_predadv-tgt", aee_adv_tgt), ("aee_pred-predadv", aee_adv_pred),
-                            ("aee_predadv-gt", self.aee_adv_gt))
-        l2_delta1, l2_delta2, l2_delta12 = logging.calc_delta_metrics(delta1, delta2, curr_step)
-        logging.log_metrics(curr_step, ("l2_delta1", l2_delta1), ("l2_delta2", l2_delta2),
-                            ("l2_delta-avg", l2_delta12))
-        self.aee_adv_tgt, self.aee_adv_pred = aee_adv_tgt, aee_adv_pred
-        self.l2_delta1, self.l2_delta2, self.l2_delta12 = l2_delta1, l2_delta2, l2_delta12
-
-        update_minima, self.delta_below_threshold = best_iterate_rule(
-            self.delta_below_threshold, l2_delta12, aee_adv_tgt, self.delta12_min_val, self.aee_adv_tgt_min_val,
-            args.delta_bound)
-        if update_minima:
-            self.delta12_min_val = l2_delta12
-            self.aee_adv_tgt_min_val = aee_adv_tgt
-            self.aee_adv_pred_min_val = aee_adv_pred
-            self.delta1_min = delta1.detach().clone()
-            self.delta2_min = delta2.detach().clone()
-            self.flow_pred_min = flow_pred.detach().clone()
-        logging.log_metrics(curr_step, ("aee_pred-tgt_min", self.aee_adv_tgt_min_val),
-                            ("l2_delta-avg_min", self.delta12_min_val),
-                            ("aee_pred-predadv_min", self.aee_adv_pred_min_val))
-        self.steps_done += 1
-        return aee_adv_tgt, aee_adv_pred, l2_delta12
-
-    def save(self, distortion_folder):
-        batch = self.batch
-        for tens, name in ((self.delta1, "delta1_final"), (self.delta2, "delta2_final"),
-                           (self.delta1_min, "delta1_best"), (self.delta2_min, "delta2_best"),
-                           (self.image1, "image1"), (self.image2, "image2"), (self.target, "target"),
-                           (self.flow_pred, "flow_pred_final"), (self.flow_pred_min, "flow_pred_best"),
-                           (self.flow_pred_init, "flow_pred_init")):
-            logging.save_tensor(tens, name, batch, distortion_folder)
-        if self.has_gt:
-            logging.save_tensor(self.flow_gt, "flow_gt", batch, distortion_folder)
-
-    def result(self):
-        """The reference's 12-tuple (attack_PCFA.py:294)."""
-        return (self.aee_gt, self.aee_tgt, self.aee_gt_tgt, self.aee_adv_gt, self.aee_adv_tgt, self.aee_adv_pred,
-                self.l2_delta1, self.l2_delta2, self.l2_delta12, self.aee_adv_tgt_min_val,
-                self.aee_adv_pred_min_val, self.delta12_min_val)
-
-
-def pcfa_attack(model, image1, image2, flow, batch, distortion_folder, eps_box, device, has_gt, optim_mu, args,
-                statistics_in_every_step=True):
-    """Attack one image pair; returns the reference's 12-tuple (attack_PCFA.py:40-294)."""
-    st = PairAttack(model, image1, image2, flow, batch, eps_box, device, has_gt, optim_mu, args)
-    if args.steps == 0:  # the reference returns its initial zeros for the adversarial statistics
-        st.aee_gt = st.aee_gt if has_gt else None
-    for _ in range(args.steps):
-        st.step()
-    if distortion_folder is not None and _should_save(batch, args):
-        st.save(distortion_folder)
-    return st.result()
-
-
-class _BatchGraphs:
-    """_PairGraphs for a PairBatch: the static buffers, hipGraphs and optimiser of one (shape, flags, B)."""
-
-    def __init__(self, st):
-        self.image1, self.image2 = st.image1, st.image2
-        self.images_max, self.images_min = st.images_max, st.images_min
-        self.params, self.target, self.optimizer = st.params, st.target, st.optimizer
-        self.graphed, self.repredict = st.graphed, st.repredict
-        self.owner = weakref.ref(st)
-
-    retire_owner = _PairGraphs.retire_owner
-
-
-def _batch_graph_cache(model):
-    """Graph sets of PairBatch, a cache of their own next to PCFA's pair cache (whose cap they do not count against)."""
-    cache = getattr(model, "_pcfa_pair_batch_graphs", None)
-    if cache is None:
-        cache = {}
-        try:
-            object.__setattr__(model, "_pcfa_pair_batch_graphs", cache)
-        except Exception:  # noqa: BLE001
-            return {}
-    return cache
-
-
 class _ItemRecord:
-    """What PairAttack keeps per pair besides the variables: the constant metrics, the last step's metrics, the best
-    iterate."""
+    """What an attack keeps per pair besides the variables: the pair's dataset index, the constant metrics, the last step's
+    metrics and the best iterate."""
 
     def __init__(self, batch):
         self.batch = batch
@@ -481,32 +105,66 @@ class _ItemRecord:
         self.aee_adv_tgt = self.aee_adv_pred = 0.
         self.l2_delta1 = self.l2_delta2 = self.l2_delta12 = 0.
 
+    def record(self, curr_step, delta_bound, aee_adv_tgt, aee_adv_pred, aee_adv_gt, l2_delta1, l2_delta2, l2_delta12,
+               delta1, delta2, flow_pred):
+        """One step's metrics (host floats) of this pair and the tensors they were computed from: logged under the
+        reference's names, and kept as the best iterate where the rule says so (attack_PCFA.py:199-243).  Returns the
+        step's (aee_adv_tgt, aee_adv_pred, l2_delta12)."""
+        self.aee_adv_tgt, self.aee_adv_pred, self.aee_adv_gt = aee_adv_tgt, aee_adv_pred, aee_adv_gt
+        self.l2_delta1, self.l2_delta2, self.l2_delta12 = l2_delta1, l2_delta2, l2_delta12
+        logging.log_metrics(curr_step, ("aee_predadv-tgt", aee_adv_tgt), ("aee_pred-predadv", aee_adv_pred),
+                            ("aee_predadv-gt", aee_adv_gt))
+        logging.log_metrics(curr_step, ("l2_delta1", l2_delta1), ("l2_delta2", l2_delta2),
+                            ("l2_delta-avg", l2_delta12))
+        update_minima, self.delta_below_threshold = best_iterate_rule(
+            self.delta_below_threshold, l2_delta12, aee_adv_tgt, self.delta12_min_val, self.aee_adv_tgt_min_val,
+            delta_bound)
+        if update_minima:
+            self.delta12_min_val = l2_delta12
+            self.aee_adv_tgt_min_val = aee_adv_tgt
+            self.aee_adv_pred_min_val = aee_adv_pred
+            self.delta1_min = delta1.detach().clone()
+            self.delta2_min = delta2.detach().clone()
+            self.flow_pred_min = flow_pred.detach().clone()
+        logging.log_metrics(curr_step, ("aee_pred-tgt_min", self.aee_adv_tgt_min_val),
+                            ("l2_delta-avg_min", self.delta12_min_val),
+                            ("aee_pred-predadv_min", self.aee_adv_pred_min_val))
+        return aee_adv_tgt, aee_adv_pred, l2_delta12
 
-class PairBatch:
-    """B independent PairAttacks whose closure evaluations are ONE forward and backward at batch B, on one stream, in one
-    graph: per item its own variables, target (from its own unattacked flow), L-BFGS state (lbfgs.BatchedLBFGS) and
-    best-iterate record.  Pair b's variables enter only pair b's loss term, so the gradient of the summed loss with respect
-    to them is exactly that pair's own gradient (ops.loss_delta_constraint_items); what differs from attacking the pair
-    alone is the rounding of the network's kernels at batch B (and, under the fixed-point scatters, a shift shared by the
-    batch).  With B = 1 every bit equals PairAttack's.
+    def as_tuple(self):
+        """The reference's 12-tuple (attack_PCFA.py:294)."""
+        return (self.aee_gt, self.aee_tgt, self.aee_gt_tgt, self.aee_adv_gt, self.aee_adv_tgt, self.aee_adv_pred,
+                self.l2_delta1, self.l2_delta2, self.l2_delta12, self.aee_adv_tgt_min_val,
+                self.aee_adv_pred_min_val, self.delta12_min_val)
 
-    pairs: B x (batch, image1 [1,3,H,W], image2, flow or None), all of one shape.  `step()` = BatchedLBFGS.step, one
-    re-prediction at batch B, the per-item metrics from one launch each and one read-back.  Item b's metrics are logged
-    under its own `batch * steps + step`; `result(b)` is its 12-tuple, `save(folder, b)` writes its artefacts.  Capture as
-    in PairAttack (eager fallback with a warning); the graph sets live in a cache of their own on the model, keyed by
-    PairAttack's key + (B,), LRU with Config.max_cached_shapes entries."""
 
-    def __init__(self, model, pairs, eps_box, device, has_gt, optim_mu, args, use_graph=None):
+class _AttackState:
+    """What PairAttack and PairBatch share: the variables of `len(self.rec)` image pairs stacked along the batch dimension,
+    the static buffers their closure reads, the target(s), the closure and its capture, and the graph set the next pair(s)
+    of the same key adopt (graph_sets).  A class adds its record(s) `rec`, `closure_body`, its optimiser, the constant
+    metrics and `step()`.
+
+    On the GPU the closure (static shapes, variables updated in place by L-BFGS) and the re-prediction forward are captured
+    once per key into hipGraphs and replayed (`use_graph=None`: on for CUDA devices unless PCFA_HIP_GRAPH=0; if capture
+    fails the eager closure -- the same kernels in the same order -- is used and a warning is logged).  A pair of the same
+    shape and flags as an earlier one copies its images / initial variables / target into that pair's buffers and resets
+    the optimiser -- no warm-up, no re-capture (`reuse_graphs`, default Config.reuse_pair_graphs; results equal a fresh
+    capture: tests/test_gpu_parity.py::test_pair_graph_reuse_equals_fresh_capture)."""
+
+    CACHE = None      # the key of graph_sets.CACHES under which this class keeps its graph sets
+    KEPT = ("image1", "image2", "images_max", "images_min", "params", "target", "optimizer", "graphed", "repredict")
+
+    def __init__(self, model, image1, image2, flow, eps_box, device, has_gt, optim_mu, args, use_graph, reuse_graphs,
+                 key_tail=(), adopt=True):
         self.model, self.args, self.device = model, args, device
         self.has_gt, self.optim_mu, self.eps_box = has_gt, optim_mu, eps_box
-        self.items = B = len(pairs)
-        self.rec = [_ItemRecord(batch) for batch, _, _, _ in pairs]
-        shapes = {tuple(p[1].shape) for p in pairs} | {tuple(p[2].shape) for p in pairs}
-        if len(shapes) != 1 or next(iter(shapes))[0] != 1:
-            raise ValueError("PairBatch: every pair is two [1,3,H,W] images of one shape, got %s" % sorted(shapes))
-        image1 = torch.cat([p[1] for p in pairs]).to(device)
-        image2 = torch.cat([p[2] for p in pairs]).to(device)
-        self.flow_gt = torch.cat([p[3] for p in pairs]).to(device) if has_gt else None
+        if reuse_graphs is None:   # pairs of one shape share static buffers + hipGraphs unless the model's config says no
+            reuse_graphs = config.cfg(model).reuse_pair_graphs
+        self.reuse_graphs = reuse_graphs
+        items = len(self.rec)
+
+        image1, image2 = image1.to(device), image2.to(device)
+        self.flow_gt = flow.to(device) if flow is not None else None
         if not ownutilities.model_takes_unit_input(args.net):
             image1 = image1 / 255.
             image2 = image2 / 255.
@@ -518,27 +176,23 @@ class PairBatch:
                              "defined. Please use --boxconstraint=clipping.")
         if use_graph is None:
             use_graph = _graphs_enabled(device, args)
-        self.graph_key = (args.net, (1,) + tuple(image1.shape[1:]), args.boxconstraint, joint, args.loss, float(optim_mu),
-                          float(args.delta_bound), float(eps_box), str(device), ops.core.current_lane(), B)
-        cache = _batch_graph_cache(model)
-        kept = cache.get(self.graph_key) if (use_graph and config.cfg(model).reuse_pair_graphs) else None
-        self.graphs_reused = kept is not None
+        self.lane = ops.core.current_lane()
+        self.graph_key = (args.net, (image1.shape[0] // items,) + tuple(image1.shape[1:]), args.boxconstraint, joint,
+                          args.loss, float(optim_mu), float(args.delta_bound), float(eps_box), str(device),
+                          self.lane) + key_tail
         self.retired = False
+
+        # the static buffers: an earlier pair's of the same key (with its graphs and optimiser; that pair is retired), or new
+        kept = graph_sets.adopt(self._graph_sets(), self.graph_key, self) if (use_graph and reuse_graphs and adopt) else None
+        self.graphs_reused = kept is not None
         if kept is not None:
-            kept.retire_owner()
-            kept.owner = weakref.ref(self)
-            self._cache_put(kept)
-            self.image1, self.image2 = kept.image1, kept.image2
-            self.images_max, self.images_min = kept.images_max, kept.images_min
-            self.params, self.target, self.optimizer = kept.params, kept.target, kept.optimizer
-            self.graphed, self.repredict = kept.graphed, kept.repredict
             self.optimizer.reset()
         else:
             self.image1, self.image2 = torch.empty_like(image1), torch.empty_like(image2)
             self.images_max, self.images_min = torch.empty_like(image1), torch.empty_like(image1)
             self.params = [torch.zeros_like(image1).requires_grad_() for _ in range(1 if joint else 2)]
             self.target = None
-            self.optimizer = ops.get().BatchedLBFGS(self.params, items=B, max_iter=10)
+            self.optimizer = self._make_optimizer()
             self.graphed = self.repredict = None
         with torch.no_grad():
             self.image1.copy_(image1)
@@ -564,33 +218,27 @@ class PairBatch:
             self.nw_input1, self.nw_input2 = self.params
             self.fwd_kwargs = {}
 
-        # the unattacked flow of every item (the forward at the initial variables) and, from it, the item's own target
+        # the unattacked flow (the forward at the initial variables) and, from it, every pair's own target
         if self.repredict is not None:
             _, flow0 = self.repredict()
         else:
             with torch.no_grad():
                 flow0 = self.predict()
         self.flow_pred_init = flow0.detach().clone()
-        target = torch.cat([targets.get_target(args.target, self.flow_pred_init[b:b + 1],
-                                               custom_target_path=args.custom_target_path, device=device).to(device)
-                            for b in range(B)])
+        target = [targets.get_target(args.target, self._item(self.flow_pred_init, b),
+                                     custom_target_path=args.custom_target_path, device=device).to(device)
+                  for b in range(items)]
+        target = target[0] if items == 1 else torch.cat(target)
         if self.target is None:
-            self.target = target.clone()
+            self.target = target
         else:
             self.target.copy_(target)
-        if kept is not None:
-            kept.target = self.target
         self.target.requires_grad = False
 
-        om = ops.get()
-        const = [om.avg_epe_items(self.target, self.flow_pred_init)]
-        if has_gt:
-            const += [om.avg_epe_items(self.target, self.flow_gt), om.avg_epe_items(self.flow_pred_init, self.flow_gt)]
-        const = torch.stack(const).tolist()
-        for b, r in enumerate(self.rec):
-            r.aee_tgt = const[0][b]
+        for r, const in zip(self.rec, self._constant_metrics()):
+            r.aee_tgt = const[0]
             if has_gt:
-                r.aee_gt_tgt, r.aee_gt = const[1][b], const[2][b]
+                r.aee_gt_tgt, r.aee_gt = const[1:]
             curr_step = r.batch * args.steps
             logging.log_metrics(curr_step, ("aee_pred-tgt", r.aee_tgt), ("aee_gt-tgt", r.aee_gt_tgt),
                                 ("aee_pred-gt", r.aee_gt))
@@ -600,30 +248,221 @@ class PairBatch:
         self.flow_pred = self.flow_pred_init
         self.delta1, self.delta2 = torch.zeros_like(self.image1), torch.zeros_like(self.image2)
         self.steps_done = 0
-        self.closures = 0          # evaluations of the batched closure (each one is a closure evaluation of every item)
+        self.closures = 0          # evaluations of the closure (each one is a closure evaluation of every item)
         if use_graph and kept is None:
             self.enable_graph()
 
-    def _cache_put(self, kept):
-        cache, cap = _batch_graph_cache(self.model), _max_cached_shapes(self.model)
-        cache.pop(self.graph_key, None)
-        cache[self.graph_key] = kept             # most recently used last
-        while len(cache) > cap:
-            old_key = next(iter(cache))
-            old = cache.pop(old_key)
-            _log_eviction("pair-batch-graph", old_key)
-            old.retire_owner()
-            old.graphed = old.repredict = old.optimizer = None
+    def _graph_sets(self):
+        return graph_sets.cache(self.model, self.CACHE)
 
-    predict = PairAttack.predict
-    current_deltas = PairAttack.current_deltas
-    _repredict_body = PairAttack._repredict_body
-    _retire = PairAttack._retire
+    def _item(self, tens, b):
+        """Pair b's rows of a tensor stacked over the pairs."""
+        n = tens.shape[0] // len(self.rec)
+        return tens[b * n:(b + 1) * n]
+
+    # ---- pieces of the closure (attack_PCFA.py:175-192) ---------------------------------------------------------
+    def predict(self):
+        out = ownutilities.compute_flow(self.model, "scaled_input_model", self.nw_input1, self.nw_input2,
+                                        test_mode=True, **self.fwd_kwargs)
+        [out] = ownutilities.postprocess_flow(self.args.net, self.padder, out)
+        return out
+
+    def current_deltas(self):
+        if self.args.joint_perturbation:
+            return extract_deltas_joint(self.nw_delta, self.images_max, self.images_min)
+        return extract_deltas(self.nw_input1, self.nw_input2, self.image1, self.image2, self.args.boxconstraint,
+                              eps_box=self.eps_box)
+
+    def _repredict_body(self):
+        return self.current_deltas(), self.predict()
+
+    def enable_graph(self, **how):
+        try:
+            self._capture(**how)
+        except Exception as e:  # noqa: BLE001 -- the eager closure launches the same kernels in the same order
+            import logging as pylog
+            pylog.warning("hipGraph capture of the closure failed (%r): launching eagerly", e)
+            self.graphed = self.repredict = None
+
+    def _capture(self):
+        from .graphed import GraphedClosure, GraphedForward
+        sink = getattr(self.optimizer, "flat_grad_views", None)
+        self.graphed = GraphedClosure(self.closure_body, self.params, grad_sink=sink() if sink else None)
+        self.repredict = GraphedForward(self._repredict_body, self.device)
+        if self.reuse_graphs and hasattr(self.optimizer, "reset"):   # the next pair of this key adopts them
+            graph_sets.put(self._graph_sets(), self.graph_key, graph_sets.GraphSet(self, self.lane, self.KEPT),
+                           _max_cached_shapes(self.model), self.CACHE)
+
+    def _retire(self):
+        """A later pair of the same key took over this one's static buffers, graphs and optimiser (or the set was evicted
+        from the per-model cache): results recorded so far stay readable, further evaluation raises."""
+        self.retired = True
+        self.graphed = self.repredict = None
 
     def _check_live(self):
         if self.retired:
-            raise RuntimeError("this PairBatch was retired: a later batch of the same shape adopted its static buffers, "
-                               "graphs and optimiser")
+            raise RuntimeError("this %s was retired: a later one of the same shape adopted its static buffers, graphs and "
+                               "optimiser (one live attack per shape, model and lane; reuse_graphs=False keeps pairs "
+                               "independent)" % type(self).__name__)
+
+    def closure(self):
+        self._check_live()
+        self.closures += 1
+        if self.graphed is not None:
+            return self.graphed()
+        for p_ in self.params:
+            p_.grad = None
+        return self.closure_body()
+
+    # ---- one `--steps` iteration (attack_PCFA.py:155-247) -------------------------------------------------------
+    def _optimise(self):
+        """The optimiser's step (10 closure evaluations) and the re-prediction at the new variables; returns the number of
+        steps done before and the new (delta1, delta2, flow_pred).  The class's `step()` adds the metrics."""
+        self._check_live()
+        steps = self.steps_done
+        for r in self.rec:
+            logging.log_metrics(r.batch * self.args.steps + steps, ("batch", r.batch), ("steps", steps), ("epoch", 0))
+
+        self.optimizer.step(self.closure)
+
+        if self.repredict is not None:
+            (delta1, delta2), flow_pred = self.repredict()
+        else:
+            with torch.no_grad():
+                (delta1, delta2), flow_pred = self._repredict_body()
+        self.delta1, self.delta2, self.flow_pred = delta1, delta2, flow_pred
+        return steps, delta1, delta2, flow_pred
+
+    def save(self, distortion_folder, b=0):
+        r = self.rec[b]
+        for tens, name in ((self._item(self.delta1, b), "delta1_final"), (self._item(self.delta2, b), "delta2_final"),
+                           (r.delta1_min, "delta1_best"), (r.delta2_min, "delta2_best"),
+                           (self._item(self.image1, b), "image1"), (self._item(self.image2, b), "image2"),
+                           (self._item(self.target, b), "target"), (self._item(self.flow_pred, b), "flow_pred_final"),
+                           (r.flow_pred_min, "flow_pred_best"), (self._item(self.flow_pred_init, b), "flow_pred_init")):
+            logging.save_tensor(tens, name, r.batch, distortion_folder)
+        if self.has_gt:
+            logging.save_tensor(self._item(self.flow_gt, b), "flow_gt", r.batch, distortion_folder)
+
+    def result(self, b=0):
+        """Pair b's 12-tuple (attack_PCFA.py:294)."""
+        return self.rec[b].as_tuple()
+
+
+class PairAttack(_AttackState, _ItemRecord):
+    """Everything pcfa_attack holds for ONE image pair (attack_PCFA.py:40-247): the optimisation variables,
+    the optimiser, the target, the best-iterate bookkeeping (the pair is its own record) -- and `step()`, the body of the
+    `--steps` loop.
+
+    `pcfa_attack` is `PairAttack(...)` + `args.steps` x `step()`; bench.py times `step()` of this class, so the
+    measured loop IS the product loop.  Capture and graph-set reuse: _AttackState."""
+
+    CACHE = "pair-graph"
+    rec = property(lambda self: (self,))
+
+    def __init__(self, model, image1, image2, flow, batch, eps_box, device, has_gt, optim_mu, args, use_graph=None,
+                 reuse_graphs=None):
+        _ItemRecord.__init__(self, batch)
+        _AttackState.__init__(self, model, image1, image2, flow, eps_box, device, has_gt, optim_mu, args, use_graph,
+                              reuse_graphs, adopt=os.environ.get("PCFA_SHARED_FORWARD", "0") != "1")
+
+    def _make_optimizer(self):
+        return ops.get().LBFGS(self.params, max_iter=10)
+
+    def _constant_metrics(self):
+        const = (logging.calc_metrics_const(self.target, self.flow_pred_init),)
+        if self.has_gt:
+            const += logging.calc_metrics_const_gt(self.target, self.flow_pred_init, self.flow_gt)
+        return [const]
+
+    def _forward_with_loss(self):
+        """closure_body without the backward: (loss, ((delta1, delta2), flow)) -- see graphed.SplitGraphedClosure."""
+        flow = self.predict()
+        d1, d2 = self.current_deltas()
+        loss = losses.loss_delta_constraint(flow, self.target, d1, d2, self.device, delta_bound=self.args.delta_bound,
+                                            mu=self.optim_mu, f_type=self.args.loss)
+        return loss, ((d1, d2), flow)
+
+    def closure_body(self):
+        loss_closure, _ = self._forward_with_loss()
+        loss_closure.backward()
+        return loss_closure
+
+    def _capture(self, share_forward=None):
+        """share_forward (default: PCFA_SHARED_FORWARD=1, off otherwise): capture the closure as forward + backward graphs
+        and let the re-prediction after a step double as the forward of the next step's first closure evaluation (such a
+        pair never enters the graph-set cache)."""
+        if share_forward is None:
+            share_forward = os.environ.get("PCFA_SHARED_FORWARD", "0") == "1"
+        if not share_forward:
+            return super()._capture()
+        from .graphed import SplitGraphedClosure
+        split = SplitGraphedClosure(self._forward_with_loss, self.params)
+        self.graphed = split
+
+        def repredict():
+            _, ((d1, d2), flow) = split.forward()
+            return (d1.detach(), d2.detach()), flow.detach()
+        self.repredict = repredict
+
+    def step(self):
+        steps, delta1, delta2, flow_pred = self._optimise()
+        aee_adv_tgt, aee_adv_pred = logging.calc_metrics_adv(flow_pred, self.target, self.flow_pred_init)
+        aee_adv_gt = logging.calc_metrics_adv_gt(flow_pred, self.flow_gt) if self.has_gt else None
+        curr_step = self.batch * self.args.steps + steps
+        l2_delta1, l2_delta2, l2_delta12 = logging.calc_delta_metrics(delta1, delta2, curr_step)
+        out = self.record(curr_step, self.args.delta_bound, aee_adv_tgt, aee_adv_pred, aee_adv_gt, l2_delta1, l2_delta2,
+                          l2_delta12, delta1, delta2, flow_pred)
+        self.steps_done += 1
+        return out
+
+
+def pcfa_attack(model, image1, image2, flow, batch, distortion_folder, eps_box, device, has_gt, optim_mu, args,
+                statistics_in_every_step=True):
+    """Attack one image pair; returns the reference's 12-tuple (attack_PCFA.py:40-294; with `--steps 0` its initial zeros
+    for the adversarial statistics)."""
+    st = PairAttack(model, image1, image2, flow, batch, eps_box, device, has_gt, optim_mu, args)
+    for _ in range(args.steps):
+        st.step()
+    if distortion_folder is not None and _should_save(batch, args):
+        st.save(distortion_folder)
+    return st.result()
+
+
+class PairBatch(_AttackState):
+    """B independent PairAttacks whose closure evaluations are ONE forward and backward at batch B, on one stream, in one
+    graph: per item its own variables, target (from its own unattacked flow), L-BFGS state (lbfgs.BatchedLBFGS) and
+    best-iterate record.  Pair b's variables enter only pair b's loss term, so the gradient of the summed loss with respect
+    to them is exactly that pair's own gradient (ops.loss_delta_constraint_items); what differs from attacking the pair
+    alone is the rounding of the network's kernels at batch B (and, under the fixed-point scatters, a shift shared by the
+    batch).  With B = 1 every bit equals PairAttack's.
+
+    pairs: B x (batch, image1 [1,3,H,W], image2, flow or None), all of one shape.  `step()` = BatchedLBFGS.step, one
+    re-prediction at batch B, the per-item metrics from one launch each and one read-back.  Item b's metrics are logged
+    under its own `batch * steps + step`; `result(b)` is its 12-tuple, `save(folder, b)` writes its artefacts.  The graph
+    sets live in a cache of their own on the model, keyed by PairAttack's key + (B,)."""
+
+    CACHE = "pair-batch-graph"
+
+    def __init__(self, model, pairs, eps_box, device, has_gt, optim_mu, args, use_graph=None):
+        self.items = B = len(pairs)
+        self.rec = [_ItemRecord(batch) for batch, _, _, _ in pairs]
+        shapes = {tuple(p[1].shape) for p in pairs} | {tuple(p[2].shape) for p in pairs}
+        if len(shapes) != 1 or next(iter(shapes))[0] != 1:
+            raise ValueError("PairBatch: every pair is two [1,3,H,W] images of one shape, got %s" % sorted(shapes))
+        super().__init__(model, torch.cat([p[1] for p in pairs]), torch.cat([p[2] for p in pairs]),
+                         torch.cat([p[3] for p in pairs]) if has_gt else None, eps_box, device, has_gt, optim_mu, args,
+                         use_graph, None, key_tail=(B,))
+
+    def _make_optimizer(self):
+        return ops.get().BatchedLBFGS(self.params, items=self.items, max_iter=10)
+
+    def _constant_metrics(self):
+        om = ops.get()
+        const = [om.avg_epe_items(self.target, self.flow_pred_init)]
+        if self.has_gt:
+            const += [om.avg_epe_items(self.target, self.flow_gt), om.avg_epe_items(self.flow_pred_init, self.flow_gt)]
+        return zip(*torch.stack(const).tolist())
 
     def closure_body(self):
         """Forward at batch B, the per-item losses, ONE backward of their sum; returns the B losses."""
@@ -635,44 +474,10 @@ class PairBatch:
         total.backward()
         return item_losses
 
-    def enable_graph(self):
-        try:
-            from .graphed import GraphedClosure, GraphedForward
-            self.graphed = GraphedClosure(self.closure_body, self.params, grad_sink=self.optimizer.flat_grad_views())
-            self.repredict = GraphedForward(self._repredict_body, self.device)
-            if config.cfg(self.model).reuse_pair_graphs:
-                self._cache_put(_BatchGraphs(self))
-        except Exception as e:  # noqa: BLE001 -- the eager closure launches the same kernels in the same order
-            import logging as pylog
-            pylog.warning("hipGraph capture of the batched closure failed (%r): launching eagerly", e)
-            self.graphed = self.repredict = None
-
-    def closure(self):
-        self._check_live()
-        self.closures += 1
-        if self.graphed is not None:
-            return self.graphed()
-        for p_ in self.params:
-            p_.grad = None
-        return self.closure_body()
-
     def step(self):
         """One `--steps` iteration for every item; returns B x (aee_adv_tgt, aee_adv_pred, l2_delta12)."""
-        self._check_live()
+        steps, delta1, delta2, flow_pred = self._optimise()
         args, om = self.args, ops.get()
-        steps = self.steps_done
-        for r in self.rec:
-            logging.log_metrics(r.batch * args.steps + steps, ("batch", r.batch), ("steps", steps), ("epoch", 0))
-
-        self.optimizer.step(self.closure)
-
-        if self.repredict is not None:
-            (delta1, delta2), flow_pred = self.repredict()
-        else:
-            with torch.no_grad():
-                (delta1, delta2), flow_pred = self._repredict_body()
-        self.delta1, self.delta2, self.flow_pred = delta1, delta2, flow_pred
-
         # the metrics of PairAttack.step per item (logging.calc_metrics_adv, calc_delta_metrics: the same fp32 operations
         # on B values at once), one read-back for all of them
         n1, n2 = delta1[0].numel(), delta2[0].numel()
@@ -683,48 +488,11 @@ class PairBatch:
         if self.has_gt:
             rows.append(om.avg_epe_items(flow_pred, self.flow_gt))
         rows = torch.stack(rows).tolist()
-        out = []
-        for b, r in enumerate(self.rec):
-            curr_step = r.batch * args.steps + steps
-            r.aee_adv_tgt, r.aee_adv_pred, r.l2_delta1, r.l2_delta2, r.l2_delta12 = (row[b] for row in rows[:5])
-            r.aee_adv_gt = rows[5][b] if self.has_gt else None
-            logging.log_metrics(curr_step, ("aee_predadv-tgt", r.aee_adv_tgt), ("aee_pred-predadv", r.aee_adv_pred),
-                                ("aee_predadv-gt", r.aee_adv_gt))
-            logging.log_metrics(curr_step, ("l2_delta1", r.l2_delta1), ("l2_delta2", r.l2_delta2),
-                                ("l2_delta-avg", r.l2_delta12))
-            update_minima, r.delta_below_threshold = best_iterate_rule(
-                r.delta_below_threshold, r.l2_delta12, r.aee_adv_tgt, r.delta12_min_val, r.aee_adv_tgt_min_val,
-                args.delta_bound)
-            if update_minima:
-                r.delta12_min_val = r.l2_delta12
-                r.aee_adv_tgt_min_val = r.aee_adv_tgt
-                r.aee_adv_pred_min_val = r.aee_adv_pred
-                r.delta1_min = delta1[b:b + 1].detach().clone()
-                r.delta2_min = delta2[b:b + 1].detach().clone()
-                r.flow_pred_min = flow_pred[b:b + 1].detach().clone()
-            logging.log_metrics(curr_step, ("aee_pred-tgt_min", r.aee_adv_tgt_min_val),
-                                ("l2_delta-avg_min", r.delta12_min_val),
-                                ("aee_pred-predadv_min", r.aee_adv_pred_min_val))
-            out.append((r.aee_adv_tgt, r.aee_adv_pred, r.l2_delta12))
+        out = [r.record(r.batch * args.steps + steps, args.delta_bound, rows[0][b], rows[1][b],
+                        rows[5][b] if self.has_gt else None, rows[2][b], rows[3][b], rows[4][b],
+                        delta1[b:b + 1], delta2[b:b + 1], flow_pred[b:b + 1]) for b, r in enumerate(self.rec)]
         self.steps_done += 1
         return out
-
-    def save(self, distortion_folder, b):
-        r, s = self.rec[b], slice(b, b + 1)
-        for tens, name in ((self.delta1[s], "delta1_final"), (self.delta2[s], "delta2_final"),
-                           (r.delta1_min, "delta1_best"), (r.delta2_min, "delta2_best"),
-                           (self.image1[s], "image1"), (self.image2[s], "image2"), (self.target[s], "target"),
-                           (self.flow_pred[s], "flow_pred_final"), (r.flow_pred_min, "flow_pred_best"),
-                           (self.flow_pred_init[s], "flow_pred_init")):
-            logging.save_tensor(tens, name, r.batch, distortion_folder)
-        if self.has_gt:
-            logging.save_tensor(self.flow_gt[s], "flow_gt", r.batch, distortion_folder)
-
-    def result(self, b):
-        """Item b's 12-tuple, as PairAttack.result."""
-        r = self.rec[b]
-        return (r.aee_gt, r.aee_tgt, r.aee_gt_tgt, r.aee_adv_gt, r.aee_adv_tgt, r.aee_adv_pred, r.l2_delta1, r.l2_delta2,
-                r.l2_delta12, r.aee_adv_tgt_min_val, r.aee_adv_pred_min_val, r.delta12_min_val)
 
 
 def group_pairs(stream, per_closure, shape_of):
@@ -863,6 +631,12 @@ def _hardware_queues_for(nflight):
     os.environ["GPU_MAX_HW_QUEUES"] = "8"
 
 
+def _result_row(batch, result):
+    """The 13-wide row attack_l2 gathers for one pair: its index and its 12-tuple, what does not exist (no ground truth) as
+    NaN."""
+    return (batch,) + tuple(float('nan') if v is None else float(v) for v in result)
+
+
 def attack_l2(args, data_loader=None, has_gt=None):
     """PCFA on every pair of a dataset, one perturbation (pair) per image pair (attack_PCFA.py:570-701).
 
@@ -899,7 +673,7 @@ def attack_l2(args, data_loader=None, has_gt=None):
             for batch, image1, image2, flow in group:
                 res = pcfa_attack(model, image1, image2, flow, batch, distortion_folder, EPS_BOX, device, has_gt, optim_mu,
                                   args)
-                local.append((batch,) + tuple(float('nan') if v is None else float(v) for v in res))
+                local.append(_result_row(batch, res))
             return
         # the pairs of a dataset are independent (attack_PCFA.py:668-670): lane k = stream + graph set + scratch of its own,
         # every pair's result bit-identical to attacking it alone (PairsInFlight)
@@ -908,11 +682,9 @@ def attack_l2(args, data_loader=None, has_gt=None):
         if args.steps > 0:
             flight.run(args.steps)
         for (batch, _, _, _), st in zip(group, flight.attacks):
-            if args.steps == 0:
-                st.aee_gt = st.aee_gt if has_gt else None
             if distortion_folder is not None and _should_save(batch, args):
                 st.save(distortion_folder)
-            local.append((batch,) + tuple(float('nan') if v is None else float(v) for v in st.result()))
+            local.append(_result_row(batch, st.result()))
 
     def attack_batch(group):
         # one closure for the whole group (PairBatch): every pair keeps its own variables, target, optimiser state and
@@ -925,7 +697,7 @@ def attack_l2(args, data_loader=None, has_gt=None):
         for b, (batch, _, _, _) in enumerate(group):
             if distortion_folder is not None and _should_save(batch, args):
                 pb.save(distortion_folder, b)
-            local.append((batch,) + tuple(float('nan') if v is None else float(v) for v in pb.result(b)))
+            local.append(_result_row(batch, pb.result(b)))
 
     mine = ((batch, image1, image2, flow) for batch, (image1, image2, flow, _) in enumerate(data_loader)
             if batch % world == rank)

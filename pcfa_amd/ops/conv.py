@@ -467,7 +467,7 @@ def _conv_workspace(device, nbytes):
                                "shape ran before it)")
         if ws is not None:
             # never free a scratch buffer a captured hipGraph may have baked in (pcfa_conv3x3_run's split-K partials):
-            # graphs are kept across pairs (attack_PCFA._PairGraphs), and a replay after the buffer grew for another
+            # graphs are kept across pairs (pcfa_amd.graph_sets), and a replay after the buffer grew for another
             # shape would write into memory the allocator has handed to someone else
             _CONV_WS_RETIRED.append(ws)
         ws = torch.empty((nbytes + 3) // 4, device=device, dtype=torch.float32)

@@ -141,7 +141,7 @@ def test_second_pair_reuses_the_graphs(monkeypatch):
     model, a, b = _model("RAFT"), _pair("RAFT", 5), _pair("RAFT", 6)
     first = _run(model, a, args, use_graph=True, reuse_graphs=True)
     assert len(captures) == 1 and not first.graphs_reused
-    kept = attack_FGSM._fgsm_graph_cache(model)[first.graph_key]
+    kept = model._pcfa_fgsm_graphs[first.graph_key]
     assert kept.captures == 1 and kept.pairs == 1 and kept.graphed is first.graphed
     first_delta, first_result = first.delta1.clone(), first.result()
     second = _run(model, b, args, batch=1, use_graph=True, reuse_graphs=True)

@@ -1,7 +1,7 @@
 """Host side of the I-FGSM product loop on the CPU port (oracle operator table, which has no `fgsm_step`): the flag, the
-refusal of lanes without a GPU, the torch fallback with its history, `steps == 0`, the per-lane LRU of the graph cache, and
-the census of the step kernel's crafted cases (tests/fgsm_cases.py; the kernel itself: tests/test_fgsm_step_gpu.py)."""
-import weakref
+refusal of lanes without a GPU, the torch fallback with its history, `steps == 0`, and the census of the step kernel's
+crafted cases (tests/fgsm_cases.py; the kernel itself: tests/test_fgsm_step_gpu.py).  The per-lane LRU of the graph cache:
+tests/test_graph_sets_cpu.py."""
 from argparse import Namespace
 
 import numpy as np
@@ -118,40 +118,6 @@ def test_zero_steps_returns_what_eager_returned():
     got = attack_FGSM.fgsm_attack(model, *pair, dev, True, args)
     assert got.pop("history") == []
     assert got == want and got["l2_delta-avg"] == 0.0
-
-
-class _Owner:
-    retired = False
-
-    def _retire(self):
-        self.retired = True
-
-
-def _kept(owner):
-    k = attack_FGSM._FgsmGraphs.__new__(attack_FGSM._FgsmGraphs)
-    k.owner, k.graphed = weakref.ref(owner), object()
-    return k
-
-
-def test_graph_cache_is_lru_per_lane():
-    cache, owners = {}, {}
-
-    def put(shape, lane):
-        key = ("RAFT", shape, shape, "aee", False, 0.00025, "zero", "cuda:0", lane)
-        owners[key] = _Owner()
-        attack_FGSM._fgsm_cache_put(cache, key, _kept(owners[key]), 2)
-        return key
-    keys = [put(shape, lane) for shape in ("A", "B") for lane in range(5)]
-    assert len(cache) == 10 and not any(o.retired for o in owners.values())    # cap 2 PER LANE: nothing evicted
-    third = put("C", 3)
-    gone = ("RAFT", "A", "A", "aee", False, 0.00025, "zero", "cuda:0", 3)
-    assert gone not in cache and owners[gone].retired                          # the oldest shape of lane 3 ...
-    assert third in cache and len(cache) == 10
-    assert all(k in cache and not owners[k].retired for k in keys if k != gone)   # ... and nothing of another lane
-    # a hit makes a set the most recently used one of its lane
-    attack_FGSM._fgsm_cache_put(cache, keys[5 + 3], cache[keys[5 + 3]], 2)     # ("B", lane 3)
-    put("D", 3)
-    assert third not in cache and owners[third].retired and keys[5 + 3] in cache
 
 
 def test_census_of_the_crafted_step_cases():

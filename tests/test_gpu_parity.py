@@ -2684,7 +2684,7 @@ def test_fresh_processes_are_bit_identical(net, size, extra, seeds, steps):
 
 def test_conv_workspace_never_frees_a_captured_buffer():
     """the split-K scratch of pcfa_conv3x3_run is baked into captured hipGraphs that outlive the pair
-    (attack_PCFA._PairGraphs); when a larger shape makes it grow, the old buffer must stay allocated."""
+    (pcfa_amd.graph_sets); when a larger shape makes it grow, the old buffer must stay allocated."""
     dev = torch.device(DEV)
     a = hip_ops._conv_workspace(dev, 1 << 20)
     pa = a.data_ptr()
