@@ -418,6 +418,22 @@ PCFA_API int pcfa_fgsm_step(float* x1, float* x2, const float* g1, const float* 
                             float* d1, float* d2, float epsilon, int joint, long long n, void* stream);
 PCFA_API int pcfa_fgsm_step_max_threads(void);
 
+/* Bit digest of a buffer of 32-bit words (pcfa_amd/trace.py: which operator's bits differ first between two runs; nothing
+ * in the default attack path calls it).  Word k of x has the global index i = index0 + k and the bit pattern w_i as an
+ * unsigned 32-bit value; the call OVERWRITES out4 with four 64-bit values, each taken mod 2^64:
+ *   out4[0] = sum w_i        out4[1] = sum w_i * h(i)        out4[2] = fp32 NaN patterns        out4[3] = +-Inf patterns
+ * h: the odd 64-bit mix of the index stated once in csrc/digest.hpp.  Integer sums mod 2^64 are associative and
+ * commutative, so the result is exact and independent of the launch (workgroup partials through `workspace`, then a
+ * finish; no atomics), and digests of adjacent pieces add: D(x[:a], 0) + D(x[a:], a) = D(x, 0).  x: n_words words, 4-byte
+ * aligned at any offset from a 16-byte boundary (the aligned body is read in 16-byte pieces, head and tail word by word);
+ * may be NULL only where n_words == 0, which writes four zeros and reads nothing.  out4: 8-byte aligned.  workspace:
+ * pcfa_digest_workspace_bytes() bytes, 8-byte aligned, caller-owned, uninitialised, one call in flight per workspace.
+ * A NULL or misaligned pointer is PCFA_ERR_INVALID_ARG.  (Added without a change of PCFA_ABI_VERSION, like the other
+ * additive entries.) */
+PCFA_API size_t pcfa_digest_workspace_bytes(void);
+PCFA_API int pcfa_digest_words(const void* x, unsigned long long n_words, unsigned long long index0,
+                               unsigned long long* out4, void* workspace, void* stream);
+
 /* loss_delta_constraint (helper_functions/losses.py:200-230) =
  *   get_loss(f_type, pred, target) + mu * relu((|d1|^2+|d2|^2)/(n1+n2) - bound^2)
  * pred/target: [B][2][H][W] views given by element strides (sb,sc,sh,sw) so the

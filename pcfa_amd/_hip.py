@@ -6,7 +6,7 @@ raises when handed a non-GPU tensor.
 """
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_uint, c_void_p, POINTER
+from ctypes import c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_uint, c_ulonglong, c_void_p, POINTER
 
 ABI_VERSION = 2
 LIB_PATH = os.environ.get("PCFA_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib",
@@ -94,6 +94,8 @@ SIGNATURES = {
     "pcfa_extract_deltas_joint_bwd": (c_int, [_P, _P, _P, _P, _P, c_longlong, _P]),
     "pcfa_fgsm_step": (c_int, [_P] * 8 + [c_float, c_int, c_longlong, _P]),
     "pcfa_fgsm_step_max_threads": (c_int, []),
+    "pcfa_digest_workspace_bytes": (c_size_t, []),
+    "pcfa_digest_words": (c_int, [_P, c_ulonglong, c_ulonglong, _P, _P, _P]),
     "pcfa_flow_loss_workspace_bytes": (c_size_t, []),
     "pcfa_flow_loss_fwd": (c_int, [_P, _S4, _P, _S4, c_int, c_int, c_int, _P, c_longlong, _P, c_longlong,
                                    c_float, c_float, c_int, _P, _P, _P]),

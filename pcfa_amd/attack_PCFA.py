@@ -155,8 +155,11 @@ class _AttackState:
     KEPT = ("image1", "image2", "images_max", "images_min", "params", "target", "optimizer", "graphed", "repredict")
 
     def __init__(self, model, image1, image2, flow, eps_box, device, has_gt, optim_mu, args, use_graph, reuse_graphs,
-                 key_tail=(), adopt=True):
+                 key_tail=(), adopt=True, trace=None):
         self.model, self.args, self.device = model, args, device
+        self.trace = trace   # a pcfa_amd.trace.ClosureTrace: every closure evaluation leaves its operators' digests there
+        if trace is not None:
+            adopt = False    # a traced closure's graphs hold digest launches: it neither adopts a graph set nor leaves one
         self.has_gt, self.optim_mu, self.eps_box = has_gt, optim_mu, eps_box
         if reuse_graphs is None:   # pairs of one shape share static buffers + hipGraphs unless the model's config says no
             reuse_graphs = config.cfg(model).reuse_pair_graphs
@@ -289,7 +292,7 @@ class _AttackState:
         sink = getattr(self.optimizer, "flat_grad_views", None)
         self.graphed = GraphedClosure(self.closure_body, self.params, grad_sink=sink() if sink else None)
         self.repredict = GraphedForward(self._repredict_body, self.device)
-        if self.reuse_graphs and hasattr(self.optimizer, "reset"):   # the next pair of this key adopts them
+        if self.reuse_graphs and self.trace is None and hasattr(self.optimizer, "reset"):   # the next pair of this key adopts them
             graph_sets.put(self._graph_sets(), self.graph_key, graph_sets.GraphSet(self, self.lane, self.KEPT),
                            _max_cached_shapes(self.model), self.CACHE)
 
@@ -309,10 +312,14 @@ class _AttackState:
         self._check_live()
         self.closures += 1
         if self.graphed is not None:
-            return self.graphed()
-        for p_ in self.params:
-            p_.grad = None
-        return self.closure_body()
+            loss = self.graphed()
+        else:
+            for p_ in self.params:
+                p_.grad = None
+            loss = self.closure_body()
+        if self.trace is not None:   # (the warm-up and capture evaluations do not come through here)
+            self.trace.keep(self.closures - 1, step=self.steps_done)
+        return loss
 
     # ---- one `--steps` iteration (attack_PCFA.py:155-247) -------------------------------------------------------
     def _optimise(self):
@@ -361,10 +368,10 @@ class PairAttack(_AttackState, _ItemRecord):
     rec = property(lambda self: (self,))
 
     def __init__(self, model, image1, image2, flow, batch, eps_box, device, has_gt, optim_mu, args, use_graph=None,
-                 reuse_graphs=None):
+                 reuse_graphs=None, trace=None):
         _ItemRecord.__init__(self, batch)
         _AttackState.__init__(self, model, image1, image2, flow, eps_box, device, has_gt, optim_mu, args, use_graph,
-                              reuse_graphs, adopt=os.environ.get("PCFA_SHARED_FORWARD", "0") != "1")
+                              reuse_graphs, adopt=os.environ.get("PCFA_SHARED_FORWARD", "0") != "1", trace=trace)
 
     def _make_optimizer(self):
         return ops.get().LBFGS(self.params, max_iter=10)
@@ -384,8 +391,21 @@ class PairAttack(_AttackState, _ItemRecord):
         return loss, ((d1, d2), flow)
 
     def closure_body(self):
+        if self.trace is not None:
+            return self._traced_closure_body()
         loss_closure, _ = self._forward_with_loss()
         loss_closure.backward()
+        return loss_closure
+
+    def _traced_closure_body(self):
+        """closure_body inside one pass of the trace -- warm-up, capture and eager evaluation alike, so the digest launches
+        are captured with the closure -- closed by the digests of the loss and of the variables' gradients."""
+        with self.trace.recording() as tr:
+            loss_closure, _ = self._forward_with_loss()
+            loss_closure.backward()
+            tr.record("closure loss", loss_closure.detach().reshape(1))
+            for i, p_ in enumerate(self.params):
+                tr.record("closure grad of variable %d %s" % (i, tuple(p_.shape)), p_.grad)
         return loss_closure
 
     def _capture(self, share_forward=None):
@@ -396,6 +416,8 @@ class PairAttack(_AttackState, _ItemRecord):
             share_forward = os.environ.get("PCFA_SHARED_FORWARD", "0") == "1"
         if not share_forward:
             return super()._capture()
+        if self.trace is not None:
+            raise ValueError("a traced PairAttack captures its closure as one graph: not with PCFA_SHARED_FORWARD=1")
         from .graphed import SplitGraphedClosure
         split = SplitGraphedClosure(self._forward_with_loss, self.params)
         self.graphed = split
@@ -417,13 +439,40 @@ class PairAttack(_AttackState, _ItemRecord):
         return out
 
 
+def _trace_folder(args):
+    """--trace_digests DIR (pcfa_amd.trace), refused where no per-pair closure exists to trace."""
+    folder = getattr(args, "trace_digests", "") or ""
+    if folder and max(1, int(getattr(args, "pairs_per_closure", 1))) > 1:
+        raise ValueError("--trace_digests records one pair's closure: not with --pairs_per_closure > 1")
+    if folder and getattr(args, "universal_perturbation", False):
+        raise ValueError("--trace_digests records one pair's closure: not with --universal_perturbation")
+    return folder
+
+
+def _new_trace(model, device, args):
+    """The recorder of one pair under --trace_digests (None without the flag): room for every closure evaluation that
+    `--steps` L-BFGS steps can ask for."""
+    if not _trace_folder(args):
+        return None
+    from .trace import ClosureTrace
+    return ClosureTrace(model, device, max_closures=max(1, args.steps) * 10 * 5 // 4)
+
+
+def _save_trace(st, args):
+    if st.trace is not None:
+        st.trace.save(os.path.join(_trace_folder(args), "%05d_trace.npz" % st.batch))
+        st.trace.close()
+
+
 def pcfa_attack(model, image1, image2, flow, batch, distortion_folder, eps_box, device, has_gt, optim_mu, args,
                 statistics_in_every_step=True):
     """Attack one image pair; returns the reference's 12-tuple (attack_PCFA.py:40-294; with `--steps 0` its initial zeros
     for the adversarial statistics)."""
-    st = PairAttack(model, image1, image2, flow, batch, eps_box, device, has_gt, optim_mu, args)
+    st = PairAttack(model, image1, image2, flow, batch, eps_box, device, has_gt, optim_mu, args,
+                    trace=_new_trace(model, device, args))
     for _ in range(args.steps):
         st.step()
+    _save_trace(st, args)
     if distortion_folder is not None and _should_save(batch, args):
         st.save(distortion_folder)
     return st.result()
@@ -644,6 +693,7 @@ def attack_l2(args, data_loader=None, has_gt=None):
     receives every pair's result tuple; there is no collective inside the attack.
     Returns the dict of averaged metrics (also logged under the reference's metric names).
     """
+    _trace_folder(args)
     optim_mu = default_mu(args)
     rank, world = sharding.rank(), sharding.world_size()
     distortion_folder = _output_folder(args, "_r%d" % rank if world > 1 else "")
@@ -678,10 +728,12 @@ def attack_l2(args, data_loader=None, has_gt=None):
         # the pairs of a dataset are independent (attack_PCFA.py:668-670): lane k = stream + graph set + scratch of its own,
         # every pair's result bit-identical to attacking it alone (PairsInFlight)
         flight = PairsInFlight(lambda k: PairAttack(model, group[k][1], group[k][2], group[k][3], group[k][0], EPS_BOX, device,
-                                                    has_gt, optim_mu, args), len(group), device)
+                                                    has_gt, optim_mu, args, trace=_new_trace(model, device, args)),
+                               len(group), device)
         if args.steps > 0:
             flight.run(args.steps)
         for (batch, _, _, _), st in zip(group, flight.attacks):
+            _save_trace(st, args)
             if distortion_folder is not None and _should_save(batch, args):
                 st.save(distortion_folder)
             local.append(_result_row(batch, st.result()))
@@ -889,6 +941,7 @@ class UniversalAttack:
 def attack_l2_universal(args, data_loader=None, has_gt=None):
     """One perturbation for a whole dataset (attack_PCFA.py:297-566), data parallel over the batch: see
     `UniversalAttack`.  Returns the final perturbations, the per-step metric history and how many collectives ran."""
+    _trace_folder(args)
     optim_mu = default_mu(args)
     rank, world = sharding.rank(), sharding.world_size()
     distortion_folder = _output_folder(args, "") if rank == 0 else None

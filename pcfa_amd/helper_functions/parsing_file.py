@@ -53,6 +53,11 @@ _FLAGS = [
                                          "batched closure on every GPU (per-pair mode; one forward/backward at batch B, "
                                          "per-pair variables, target, L-BFGS state and best iterate; not with "
                                          "--pairs_in_flight > 1)"), _PCFA_TRAIN),
+    ("pcfa", "--trace_digests", dict(default='', metavar='DIR', help="NEW: write DIR/NNNNN_trace.npz per pair: the bit "
+                                     "digest of every operator output and gradient of every closure evaluation "
+                                     "(pcfa_amd.trace; `python -m pcfa_amd.trace diff A B` names the first record that "
+                                     "differs between two runs; per-pair mode, not with --pairs_per_closure > 1)"),
+     _PCFA_TRAIN),
     ("pcfa", "--delta_bound", dict(default=0.005, type=float, help="bound on the per-pixel averaged L2 norm of "
                                    "the perturbation"), _PCFA_TRAIN),
     ("pcfa", "--mu", dict(default=-1, type=float, help="penalty weight; -1 = 2500/delta_bound (x1.5 for non-zero "

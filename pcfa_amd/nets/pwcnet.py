@@ -40,6 +40,12 @@ def _regrid(x, d_from, d_to, batch):
     return v.reshape(batch * d_to * d_to, C, h // r, w // r)
 
 
+def _s2_pad(x, own_bwd):
+    """Zero columns to append to x so that ops.conv_s2 serves its width in both directions: a multiple of 4 for the
+    forward kernel, of 8 for its own data gradient (own_bwd: Config.conv_s2_bwd)."""
+    return -x.shape[-1] % (8 if own_bwd else 4)
+
+
 class _ConvLeaky(nn.Sequential):
     """conv() of the reference (PWCNet.py:29-35): Conv2d + LeakyReLU(0.1); same parameter names ("0.weight", "0.bias").
     Frozen 3x3 / stride 1 / pad 1 instances run as ops.conv3x3 (Winograd on the fp32 matrix cores, bias and
@@ -82,9 +88,13 @@ class _ConvLeaky(nn.Sequential):
         if (conf.dilated_as_subgrids and d in conf.dilated_as_subgrids and c.stride == (1, 1) and c.dilation == (d, d)
                 and c.padding == (d, d) and c.out_channels >= 16 and x.shape[-2] % d == 0 and x.shape[-1] % d == 0):
             return "subgrid"
-        if (conf.conv_s2 and c.stride == (2, 2) and c.padding == (1, 1) and c.dilation == (1, 1)
-                and ops.get().conv_s2_supported(x, c.weight)):
-            return "s2"
+        if conf.conv_s2 and c.stride == (2, 2) and c.padding == (1, 1) and c.dilation == (1, 1):
+            # ops.conv_s2 serves W % 4 == 0 (W % 8 == 0 backward): other maps are asked about at the width forward() pads
+            # them to (_s2_pad)
+            pad = _s2_pad(x, conf.conv_s2_bwd)
+            probe = x if pad == 0 else x.new_empty(tuple(x.shape[:-1]) + (x.shape[-1] + pad,))
+            if ops.get().conv_s2_supported(probe, c.weight):
+                return "s2"
         return None
 
     def forward(self, x, grad_premasked=False, mask_input_grad=False, grid_in=1, grid_out=1, bgr_input=False, skip=False):
@@ -114,8 +124,17 @@ class _ConvLeaky(nn.Sequential):
             # the pyramid's stride-2 layers (PWCNet.py:87-104): direct fp32-MFMA kernel, bias + LeakyReLU in the epilogue
             if mask_input_grad:
                 raise RuntimeError("conv_s2 does not apply an input mask")
-            y = ops.get().conv_s2(_regrid(x, grid_in, 1, batch), weight, c.bias, leaky_slope=slope,
-                                  own_bwd=cfg(self).conv_s2_bwd, **kw)
+            x = _regrid(x, grid_in, 1, batch)
+            pad, w_out = _s2_pad(x, cfg(self).conv_s2_bwd), (x.shape[-1] - 1) // 2 + 1
+            if pad:
+                # W % 8 != 0 (a coarse level of an image whose width is no multiple of 256): zero columns on the right
+                # are what the layer's own padding supplies, so the first w_out output columns are the layer's -- on the
+                # same kernels as every other size, forward and backward, instead of a library convolution / a library
+                # data gradient whose sums are not repeatable
+                x = nn.functional.pad(x, (0, pad))
+            y = ops.get().conv_s2(x, weight, c.bias, leaky_slope=slope, own_bwd=cfg(self).conv_s2_bwd, **kw)
+            if pad:
+                y = y[..., :w_out].contiguous()
             return _regrid(y, 1, grid_out, batch)
         kw.update(mask_input_grad=mask_input_grad, input_slope=slope if mask_input_grad else 0.)
         # A 3x3 convolution with dilation d (the context network, PWCNet.py:160-166) never mixes pixels of different

@@ -22,6 +22,7 @@ Operator boundaries mirrored (reference file:line) -- one module per group:
   attack_math  box_transform, extract_deltas(_joint), loss_delta_constraint, avg_epe, two_norm_*, pm1_pair
                                                               helper_functions/own_models.py:62-85, attack_PCFA.py:20-37, losses.py
                fgsm_step                                      attack_FGSM.py:21-56,208-209
+  digest       tensor_digest                                  (no counterpart: the record of pcfa_amd.trace.ClosureTrace)
 """
 from .. import _hip  # noqa: F401
 from ..lbfgs import LBFGS  # noqa: F401  (the attack loop's optimiser: torch.optim.LBFGS semantics, HIP vector math)
@@ -34,6 +35,7 @@ from .core import *  # noqa: F401,F403
 from .core import _call, _dev, _ptr, _ptr_off, _stream  # noqa: F401
 from .corr import *  # noqa: F401,F403
 from .corr import _convc1_packed  # noqa: F401
+from .digest import *  # noqa: F401,F403
 from .flownet import *  # noqa: F401,F403
 from .flownet2 import *  # noqa: F401,F403
 from .gma import *  # noqa: F401,F403
