@@ -26,75 +26,28 @@
 //     read back and added to dpyr (read-modify-write of 16 B per lane).  Every
 //     window texel is owned by one lane of one workgroup: no atomics, bitwise
 //     reproducible.
-#include "common.hpp"
+#include "corr_window.hpp"
 
 namespace {
-
-constexpr int RS = 20;  // LDS row stride (floats): 4 pad + 16; window texel (r, c) sits at r*RS + 4 + c
 
 #ifndef PCFA_LOOKUP_QB
 #define PCFA_LOOKUP_QB 32
 #endif
 
-// QB = queries (= windows) per workgroup: 64 (one wave of queries per window row, 2r+1 waves), 32 (two window
-// rows per wave, r+1 waves) or 16.  Measured on MI355X at 55x128, r = 4 (rocprofv3, L2-warm / flushed):
-// forward 7.4 / 11.9 us at 64, 6.5 / 11.7 us at 32, 7.1-7.5 / 12.4 us at 16; backward 10.6 us at 32 -- more,
+// QB = queries (= windows) per workgroup (Geo<R, QB>, corr_window.hpp): 64 (one wave of queries per window row, 2r+1
+// waves), 32 (two window rows per wave, r+1 waves) or 16.  Measured on MI355X at 55x128, r = 4 (rocprofv3, L2-warm /
+// flushed): forward 7.4 / 11.9 us at 64, 6.5 / 11.7 us at 32, 7.1-7.5 / 12.4 us at 16; backward 10.6 us at 32 -- more,
 // smaller workgroups (880 x 5 waves, 3-4 per CU) overlap each other's load, LDS and store phases better.
-template <int R, int QB>
-struct Geo {
-  static_assert(QB == 64 || QB == 32 || QB == 16, "lane % QB = query needs QB to divide the wave");
-  static constexpr int N1 = 2 * R + 1;                      // taps per axis
-  static constexpr int WIN = 2 * R + 2;                     // window texels per axis
-  static constexpr int RPW = 64 / QB;                       // window rows (phase B) per wave
-  static constexpr int NW = (N1 + RPW - 1) / RPW;           // waves per workgroup
-  static constexpr int TXN = ((WIN + 2) >> 2) + 1;          // tile columns a window can cross
-  static constexpr int PIECES = WIN * TXN;                  // 16-B pieces per window
-  static constexpr int NP = (QB * PIECES + NW * 64 - 1) / (NW * 64);  // piece wave-instructions per wave
-  static constexpr bool FULL = QB * PIECES == NW * NP * 64; // every piece slot of every wave is a real piece
-  static constexpr int WS = WIN * RS + 4;                   // floats per window image; WS/4 odd -> the b128 accesses
-                                                            // of 16 consecutive windows hit 16 distinct bank groups
-  static constexpr int NRD = (WIN + 3) / 4;                 // b128 accesses per window row
-  static constexpr int LDS_FLOATS = QB * WS + 4;            // + a 16-B dump slot for lanes without a piece
-};
-
-struct Origin {
-  int x0, y0;    // window origin (texels, level coordinates)
-  float fx, fy;  // shared bilinear fractions
-};
-
-// reference: coords / 2**i  (exact power-of-two scaling), then floor / fraction
-__device__ __forceinline__ Origin make_origin(float cx, float cy, int level, int R) {
-  const float inv = 1.0f / (float)(1 << level);
-  const float xl = cx * inv, yl = cy * inv;
-  const float flx = floorf(xl), fly = floorf(yl);
-  Origin o;
-  o.fx = xl - flx;
-  o.fy = yl - fly;
-  o.x0 = (int)fminf(fmaxf(flx, -1.0e8f), 1.0e8f) - R;
-  o.y0 = (int)fminf(fmaxf(fly, -1.0e8f), 1.0e8f) - R;
-  return o;
-}
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // 16-B load at (64-bit scalar base) + (32-bit per-lane byte offset) for the lanes of `mask` only; the other
 // lanes keep the previous register contents.  Inline asm so that the compiler neither waits between the
 // back-to-back loads of a wave nor turns the mask into a branch; the caller drains them with wait_all_loads()
-// before the first use (cdna_hip_programming.md 5.7).
+// before the first use (cdna_hip_programming.md 5.7).  sbase goes through scalar_ptr: the "s" operand needs SGPRs.
 __device__ __forceinline__ void load_piece_masked(f32x4& v, const float* sbase, unsigned voff_bytes,
                                                   unsigned long long mask) {
   unsigned long long save;
   asm volatile("s_mov_b64 %1, exec\n\ts_and_b64 exec, exec, %4\n\tglobal_load_dwordx4 %0, %2, %3\n\ts_mov_b64 exec, %1"
                : "+v"(v), "=&s"(save) : "v"(voff_bytes), "s"(sbase), "s"(mask) : "memory");
-}
-
-// Pin a wave-uniform pointer into SGPRs (the "s" asm operand above needs it there).
-template <typename T>
-__device__ __forceinline__ T* scalar_ptr(T* p) {
-  const unsigned long long u = reinterpret_cast<unsigned long long>(p);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u);
-  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-  return reinterpret_cast<T*>(((unsigned long long)hi << 32) | lo);
 }
 
 template <int N>
@@ -156,8 +109,7 @@ struct Block {
   bool live;     // this lane's query exists
   Origin o;      // of this lane's query
   int myB;       // bytes from the workgroup's first slab to this query's level
-  int myXY;      // (y0 + 16) | (x0 + 16) << 16, clamped; a window that misses the level collapses onto an
-                 // out-of-range origin so that every one of its pieces is invalid
+  int myXY;      // (y0 + 16) | (x0 + 16) << 16 of the clamped origin (clamp_origin)
 
   __device__ __forceinline__ void init(const float* __restrict__ coords, int Q, const PyrLayout& P) {
     level = blockIdx.y;
@@ -178,19 +130,10 @@ struct Block {
       cy = coords[((size_t)b_img * 2 + 1) * Q + q0 + j];
     }
     o = make_origin(cx, cy, level, R);
-    const int th4 = ((hl + 3) >> 2) << 2;
-    const int x0 = min(max(o.x0, -16), 4 * tw), y0 = live ? min(max(o.y0, -16), th4) : th4;
+    const Origin c = clamp_origin(o, live, hl, tw);
     myB = (off + j * slab) * 4;
-    myXY = (y0 + 16) | ((x0 + 16) << 16);
+    myXY = (c.y0 + 16) | ((c.x0 + 16) << 16);
   }
-};
-
-struct Piece {
-  unsigned goff;  // bytes from the workgroup's first slab to the piece's 16 B in the pyramid
-  unsigned lds;   // byte address in the window image of the piece's first texel (unaligned by the window's ox)
-  int mask;       // bit e (< 4): texel e of the piece is a window texel inside the level; bit 4 ("need"): the
-                  // piece holds texels of the level at all (else: zeros / nothing to add)
-  __device__ __forceinline__ bool need() const { return (mask & 16) != 0; }
 };
 
 // Piece slot (wv*NP + i)*64 + lane of the workgroup: window = slot / PIECES (query inside the block), window row
@@ -208,6 +151,8 @@ __device__ __forceinline__ void fetch_window_params(const Block<R, QB>& blk, int
   }
 }
 
+// The piece of slot i, rebased: goff in bytes from the workgroup's first slab, lds a byte address in s_win (the dump
+// slot for a slot past the block's last window, which is never needed).
 template <int R, int QB>
 __device__ __forceinline__ Piece make_piece(const Block<R, QB>& blk, int i, int wB, int wXY) {
   using G = Geo<R, QB>;
@@ -215,19 +160,11 @@ __device__ __forceinline__ Piece make_piece(const Block<R, QB>& blk, int i, int 
   const unsigned k = p / (unsigned)G::PIECES, q = p - k * (unsigned)G::PIECES;   // k = query inside the block
   const unsigned rr = q / (unsigned)G::TXN, tx = q - rr * (unsigned)G::TXN;
   const int y0 = (int)((unsigned)wXY & 0xffffu) - 16, x0 = (int)((unsigned)wXY >> 16) - 16;
-  const int ox = x0 & 3, y = y0 + (int)rr, gtx = (x0 >> 2) + (int)tx;
   const bool mine = G::FULL || k < (unsigned)QB;
-  Piece pc;
-  const bool need = mine && (unsigned)y < (unsigned)blk.hl && (unsigned)gtx < (unsigned)blk.tw &&
-                    (int)(4 * tx) < ox + G::WIN;
-  const int c0 = (int)(4 * tx) - ox, gx0 = 4 * gtx;  // window column / level x of the piece's first texel
-  pc.mask = need ? 16 : 0;
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-    if ((unsigned)(c0 + e) < (unsigned)G::WIN && gx0 + e < blk.wl) pc.mask |= 1 << e;
-  pc.goff = (unsigned)wB + (((((unsigned)y >> 2) * (unsigned)blk.tw + (unsigned)gtx) << 4) + (((unsigned)y & 3u) << 2)) * 4u;
-  const unsigned lds = (k * G::WS + rr * RS + 4u + 4u * tx - (unsigned)ox) * 4u;
-  pc.lds = mine ? lds : (unsigned)(QB * G::WS * 4);
+  Piece pc = piece_geometry(x0, y0, (int)rr, (int)tx, blk.hl, blk.wl, blk.tw, G::WIN);
+  if (!mine) pc.mask &= 15;
+  pc.goff = (unsigned)wB + pc.goff * 4u;
+  pc.lds = (mine ? k * G::WS + pc.lds : (unsigned)(QB * G::WS)) * 4u;
   return pc;
 }
 
@@ -298,13 +235,12 @@ __device__ __forceinline__ void corr_lookup_fwd_body(
     t0[4 * i] = u0.x; t0[4 * i + 1] = u0.y; t0[4 * i + 2] = u0.z; t0[4 * i + 3] = u0.w;
     t1[4 * i] = u1.x; t1[4 * i + 1] = u1.y; t1[4 * i + 2] = u1.z; t1[4 * i + 3] = u1.w;
   }
-  const float w00 = (1.f - fx) * (1.f - fy), w01 = fx * (1.f - fy);
-  const float w10 = (1.f - fx) * fy, w11 = fx * fy;
+  const BlendWeights w = blend_weights(fx, fy);
   const int C = P.L * N1 * N1;
   float* o = out + ((size_t)blk.b_img * C + (size_t)blk.level * N1 * N1 + b) * Q + blk.q0 + j;
   float res[N1];
 #pragma unroll
-  for (int a = 0; a < N1; ++a) res[a] = t0[a] * w00 + t0[a + 1] * w01 + t1[a] * w10 + t1[a + 1] * w11;
+  for (int a = 0; a < N1; ++a) res[a] = blend4(t0[a], t0[a + 1], t1[a], t1[a + 1], w);
   if constexpr (STAMP) {
 #pragma unroll
     for (int a = 0; a < N1; ++a) asm volatile("" : "+v"(res[a]));
@@ -350,14 +286,11 @@ __device__ __forceinline__ void corr_lookup_bwd_body(
   }
   stamp<STAMP>(st, 3, false);  // dpyr loads issued
 
-  // ---- Phase A': thread (query, row) builds row `row` of the window's gradient image ----------------
-  // d window[r][c] = w00 g[c][r] + w01 g[c-1][r] + w10 g[c][r-1] + w11 g[c-1][r-1]   (g = 0 outside 0..2r)
+  // ---- Phase A': thread (query, row) builds row `row` of the window's gradient image (window_grad_row) ----
   const int row = blk.wv * G::RPW + blk.lane / QB;
   if (G::RPW * G::NW == N1 || row < N1) {
     const int j = blk.j;
-    const float fx = blk.o.fx, fy = blk.o.fy;
-    const float w00 = (1.f - fx) * (1.f - fy), w01 = fx * (1.f - fy);
-    const float w10 = (1.f - fx) * fy, w11 = fx * fy;
+    const BlendWeights w = blend_weights(blk.o.fx, blk.o.fy);
     const int C = P.L * N1 * N1;
     const float* g = grad_out + ((size_t)blk.b_img * C + (size_t)blk.level * N1 * N1) * Q + blk.q0 + j;
     float gc[N1], gp[N1];  // tap gradients of window row `row` and of the row above, along a
@@ -368,26 +301,12 @@ __device__ __forceinline__ void corr_lookup_bwd_body(
     }
     float4* dst0 = reinterpret_cast<float4*>(&s_win[j * G::WS + row * RS + 4]);
     float d[NRD * 4];
-#pragma unroll
-    for (int c = 0; c < NRD * 4; ++c) {
-      float s = 0.f;
-      if (c < N1) s = gc[c] * w00;
-      if (c >= 1 && c <= N1) s = fmaf(gc[c - 1], w01, s);
-      if (c < N1) s = fmaf(gp[c], w10, s);
-      if (c >= 1 && c <= N1) s = fmaf(gp[c - 1], w11, s);
-      d[c] = s;
-    }
+    window_grad_row<N1, NRD>(gc, gp, w, d);
 #pragma unroll
     for (int i = 0; i < NRD; ++i) dst0[i] = make_float4(d[4 * i], d[4 * i + 1], d[4 * i + 2], d[4 * i + 3]);
-    if (row == N1 - 1) {  // the owner of the last tap row also builds the window's last row (only the row above contributes)
+    if (row == N1 - 1) {  // the owner of the last tap row also builds the window's last row
       float4* dst1 = reinterpret_cast<float4*>(&s_win[j * G::WS + (WIN - 1) * RS + 4]);
-#pragma unroll
-      for (int c = 0; c < NRD * 4; ++c) {
-        float s = 0.f;
-        if (c < N1) s = gc[c] * w10;
-        if (c >= 1 && c <= N1) s = fmaf(gc[c - 1], w11, s);
-        d[c] = s;
-      }
+      window_grad_last_row<N1, NRD>(gc, w, d);
 #pragma unroll
       for (int i = 0; i < NRD; ++i) dst1[i] = make_float4(d[4 * i], d[4 * i + 1], d[4 * i + 2], d[4 * i + 3]);
     }
@@ -404,14 +323,7 @@ __device__ __forceinline__ void corr_lookup_bwd_body(
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
       const float* src = reinterpret_cast<const float*>(lds_bytes + pc[i].lds);
-      const float e0 = src[0], e1 = src[1], e2 = src[2], e3 = src[3];
-      // image cells outside the window's columns were never written; texels beyond the level width stay zero
-      const int m = pc[i].mask;
-      f32x4 t = v[i];
-      t.x += (m & 1) ? e0 : 0.f;
-      t.y += (m & 2) ? e1 : 0.f;
-      t.z += (m & 4) ? e2 : 0.f;
-      t.w += (m & 8) ? e3 : 0.f;
+      const f32x4 t = piece_add(v[i], src[0], src[1], src[2], src[3], pc[i].mask);
       if (pc[i].need()) *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(slab0) + pc[i].goff) = t;
     }
   }

@@ -20,19 +20,20 @@
 // Radius 4, 4 levels (the only configuration RAFT / GMA use, raft_config.json / gma_config.json); other shapes
 // return PCFA_ERR_UNSUPPORTED and the caller composes pcfa_corr_lookup_* with a convolution.
 #include <cstdlib>
-#include "common.hpp"
+#include "corr_window.hpp"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int R = 4, N1 = 9, WIN = 10, TXN = 4, PIECES = WIN * TXN;  // window geometry (corr_lookup.hip, Geo<4>)
-constexpr int RS = 20, WS = WIN * RS + 4, NRD = 3;                    // LDS image: row stride, window stride
+constexpr int R = 4;                                                 // radius
 constexpr int QT = 32;                                               // queries per workgroup
+using GW = Geo<R, QT>;                                               // window geometry and LDS image (corr_window.hpp)
+constexpr int N1 = GW::N1, WIN = GW::WIN, TXN = GW::TXN, PIECES = GW::PIECES, WS = GW::WS, NRD = GW::NRD;
 constexpr int NT = 256;                                              // threads that load / run the matrix work (4 waves)
 constexpr int NTF = NT + 64;                                         // forward: + one auxiliary wave (tap row 8)
 constexpr int NPC = QT * PIECES / NT;                                // 5 pieces per thread and level
+static_assert(NPC * 8 == PIECES && TXN == 4, "8 threads cover a window's pieces: q = sub + 8 i, row q >> 2, tile column q & 3");
 constexpr int L = 4, TAPS = N1 * N1;                                 // 81 taps per level
 constexpr int KL = 88, KG = KL / 8;                                  // padded tap rows per level, groups of 8 rows
 constexpr int KP = L * KL;                                           // 352 padded tap rows
@@ -54,24 +55,6 @@ constexpr int WIN_FLOATS = QT * WS + 4;
                              // 8 = per-workgroup phase timestamps instead of results
 #endif
 
-struct Origin {
-  int x0, y0;
-  float fx, fy;
-};
-
-// reference: coords / 2**i (exact power-of-two scaling), then floor / fraction -- identical to corr_lookup.hip
-__device__ __forceinline__ Origin make_origin(float cx, float cy, int level) {
-  const float inv = 1.0f / (float)(1 << level);
-  const float xl = cx * inv, yl = cy * inv;
-  const float flx = floorf(xl), fly = floorf(yl);
-  Origin o;
-  o.fx = xl - flx;
-  o.fy = yl - fly;
-  o.x0 = (int)fminf(fmaxf(flx, -1.0e8f), 1.0e8f) - R;
-  o.y0 = (int)fminf(fmaxf(fly, -1.0e8f), 1.0e8f) - R;
-  return o;
-}
-
 // A piece outside its level loads the slab's all-zero tile instead (common.hpp: P.zero): plain loads that hipcc
 // counts itself -- with 20 pieces per thread in flight across a GEMM, hand-counted inline-asm loads (corr_lookup.hip)
 // would leave 80 registers the compiler believes are already written.
@@ -87,112 +70,24 @@ __device__ __forceinline__ void store_piece(float* sbase, unsigned voff_bytes, f
   *(gptr)(reinterpret_cast<unsigned long long>(sbase) + voff_bytes) = t;
 }
 
-template <typename T>
-__device__ __forceinline__ T* scalar_ptr(T* p) {
-  const unsigned long long u = reinterpret_cast<unsigned long long>(p);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u);
-  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-  return reinterpret_cast<T*>(((unsigned long long)hi << 32) | lo);
-}
-
-struct Piece {
-  unsigned goff;  // bytes from the workgroup's first slab
-  unsigned lds;   // byte address of the piece's first texel in the window image
-  int mask;       // bits 0-3: texel is a window texel inside the level; bit 4: the piece exists in the level
-  __device__ __forceinline__ bool need() const { return (mask & 16) != 0; }
-};
-
-// Per (thread, level): the query's window origin and the thread's NPC pieces.  Piece slot p = i * NT + tid:
-// window k = p / 40 (query inside the block), window row rr, tile column tx -- as corr_lookup.hip's make_piece.
-struct LevelGeo {
-  float fx, fy;
-  Piece pc[NPC];
-};
-
-__device__ __forceinline__ void level_geometry(LevelGeo& g, float cx, float cy, bool live, int level, int j,
-                                               const PyrLayout& P, int tid) {
-  const int hl = P.h[level], wl = P.w[level], tw = P.tw[level], off = P.off[level], slab = P.slab;
-  const Origin o = make_origin(cx, cy, level);
-  g.fx = o.fx;
-  g.fy = o.fy;
-  const int th4 = ((hl + 3) >> 2) << 2;
-  const int cx0 = min(max(o.x0, -16), 4 * tw), cy0 = live ? min(max(o.y0, -16), th4) : th4;
-  const int myB = (off + j * slab) * 4;
-  const int myXY = (cy0 + 16) | ((cx0 + 16) << 16);
-#pragma unroll
-  for (int i = 0; i < NPC; ++i) {
-    const unsigned p = (unsigned)(i * NT + tid);
-    const unsigned k = p / (unsigned)PIECES, q = p - k * (unsigned)PIECES;
-    const unsigned rr = q / (unsigned)TXN, tx = q - rr * (unsigned)TXN;
-    const int wB = __builtin_amdgcn_ds_bpermute((int)(k * 4u), myB);     // lane k of this wave owns query k
-    const int wXY = __builtin_amdgcn_ds_bpermute((int)(k * 4u), myXY);
-    const int y0 = (int)((unsigned)wXY & 0xffffu) - 16, x0 = (int)((unsigned)wXY >> 16) - 16;
-    const int ox = x0 & 3, y = y0 + (int)rr, gtx = (x0 >> 2) + (int)tx;
-    const bool need = (unsigned)y < (unsigned)hl && (unsigned)gtx < (unsigned)tw && (int)(4 * tx) < ox + WIN;
-    const int c0 = (int)(4 * tx) - ox, gx0 = 4 * gtx;
-    int mask = need ? 16 : 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if ((unsigned)(c0 + e) < (unsigned)WIN && gx0 + e < wl) mask |= 1 << e;
-    g.pc[i].mask = mask;
-    g.pc[i].goff = need ? (unsigned)wB + (((((unsigned)y >> 2) * (unsigned)tw + (unsigned)gtx) << 4) + (((unsigned)y & 3u) << 2)) * 4u
-                        : (unsigned)P.zero * 4u;   // the first slab's zero tile
-    g.pc[i].lds = (k * WS + rr * RS + 4u + 4u * tx - (unsigned)ox) * 4u;
-  }
-}
-
-// Forward kernel's variant: 8 threads per query (k = tid >> 3), each owning pieces q = sub + 8 i (row q >> 2, tile column
+// Forward kernel's pieces: 8 threads per query (k = tid >> 3), each owning pieces q = sub + 8 i (row q >> 2, tile column
 // q & 3) of that query's window -- no divisions, no cross-lane traffic; the origin is recomputed from the query's own
-// coordinates.  Same piece addresses and LDS image as level_geometry (which the backward still uses: it needs the masks).
+// coordinates.  The backward kernel has the same ownership (and needs the masks as well).
 // The first version spent ~800 instructions (4 k cycles at one wave per SIMD) here before the first window load left.
 struct FwdPieces {
-  unsigned goff[NPC], lds[NPC];
+  unsigned goff[NPC], lds[NPC];   // bytes from the workgroup's first slab / byte address in the window images
 };
 __device__ __forceinline__ void fwd_pieces(FwdPieces& g, float kx, float ky, bool klive, int level, int k, int sub,
-                                           int hl, int tw, int off, int slab, int zero) {
-  static_assert(NPC * 8 == PIECES, "8 threads cover a window's pieces");
-  const Origin o = make_origin(kx, ky, level);
-  const int th4 = ((hl + 3) >> 2) << 2;
-  const int x0 = min(max(o.x0, -16), 4 * tw), y0 = klive ? min(max(o.y0, -16), th4) : th4;
-  const unsigned wB = (unsigned)(off + k * slab) * 4u;
-  const int ox = x0 & 3;
-#pragma unroll
-  for (int i = 0; i < NPC; ++i) {
-    const int q = sub + 8 * i, rr = q >> 2, tx = q & 3;
-    const int y = y0 + rr, gtx = (x0 >> 2) + tx;
-    const bool need = (unsigned)y < (unsigned)hl && (unsigned)gtx < (unsigned)tw && 4 * tx < ox + WIN;
-    g.goff[i] = need ? wB + (((((unsigned)y >> 2) * (unsigned)tw + (unsigned)gtx) << 4) + (((unsigned)y & 3u) << 2)) * 4u
-                     : (unsigned)zero * 4u;   // the first slab's zero tile
-    g.lds[i] = (unsigned)(k * WS + rr * RS + 4 + 4 * tx - ox) * 4u;
-  }
-}
-
-// Backward kernel's variant of fwd_pieces: the same ownership plus the per-texel masks of level_geometry.
-struct BwdPieces {
-  unsigned goff[NPC], lds[NPC];
-  int mask[NPC];   // bits 0-3: texel is a window texel inside the level; bit 4: the piece exists in the level
-};
-__device__ __forceinline__ void bwd_pieces(BwdPieces& g, float kx, float ky, bool klive, int level, int k, int sub,
                                            int hl, int wl, int tw, int off, int slab, int zero) {
-  const Origin o = make_origin(kx, ky, level);
-  const int th4 = ((hl + 3) >> 2) << 2;
-  const int x0 = min(max(o.x0, -16), 4 * tw), y0 = klive ? min(max(o.y0, -16), th4) : th4;
+  const Origin o = clamp_origin(make_origin(kx, ky, level, R), klive, hl, tw);
   const unsigned wB = (unsigned)(off + k * slab) * 4u;
-  const int ox = x0 & 3;
 #pragma unroll
   for (int i = 0; i < NPC; ++i) {
-    const int q = sub + 8 * i, rr = q >> 2, tx = q & 3;
-    const int y = y0 + rr, gtx = (x0 >> 2) + tx;
-    const bool need = (unsigned)y < (unsigned)hl && (unsigned)gtx < (unsigned)tw && 4 * tx < ox + WIN;
-    const int c0 = 4 * tx - ox, gx0 = 4 * gtx;
-    int mask = need ? 16 : 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if ((unsigned)(c0 + e) < (unsigned)WIN && gx0 + e < wl) mask |= 1 << e;
-    g.mask[i] = mask;
-    g.goff[i] = need ? wB + (((((unsigned)y >> 2) * (unsigned)tw + (unsigned)gtx) << 4) + (((unsigned)y & 3u) << 2)) * 4u
-                     : (unsigned)zero * 4u;
-    g.lds[i] = (unsigned)(k * WS + rr * RS + 4 + 4 * tx - ox) * 4u;
+    const int q = sub + 8 * i;
+    const Piece pc = piece_geometry(o.x0, o.y0, q >> 2, q & 3, hl, wl, tw, WIN);   // (the texel mask goes unused)
+    g.goff[i] = (unsigned)zero * 4u;   // the first slab's zero tile
+    if (pc.need()) g.goff[i] = wB + pc.goff * 4u;
+    g.lds[i] = ((unsigned)(k * WS) + pc.lds) * 4u;
   }
 }
 
@@ -266,7 +161,7 @@ __global__ __launch_bounds__(NTF) void corr_lookup_convc1_fwd_kernel(
     float fxa[L], fya[L];
 #pragma unroll
     for (int l = 0; l < L; ++l) {
-      const Origin o = make_origin(cx, cy, l);
+      const Origin o = make_origin(cx, cy, l, R);
       fxa[l] = o.fx;
       fya[l] = o.fy;
     }
@@ -277,8 +172,7 @@ __global__ __launch_bounds__(NTF) void corr_lookup_convc1_fwd_kernel(
     auto aux_blend = [&](int i) {
       if (lane < QT) {
         const int l = L - 1 - i;
-        const float fx = fxa[l], fy = fya[l];
-        const float w00 = (1.f - fx) * (1.f - fy), w01 = fx * (1.f - fy), w10 = (1.f - fx) * fy, w11 = fx * fy;
+        const BlendWeights w = blend_weights(fxa[l], fya[l]);
         const f32x4* pa = reinterpret_cast<const f32x4*>(&s_win2[i & 1][j * WS + (N1 - 1) * RS + 4]);
         const f32x4* pb = reinterpret_cast<const f32x4*>(&s_win2[i & 1][j * WS + N1 * RS + 4]);
         const f32x4 a0 = pa[0], a1 = pa[1], a2 = pa[2], b0 = pb[0], b1 = pb[1], b2 = pb[2];
@@ -286,7 +180,7 @@ __global__ __launch_bounds__(NTF) void corr_lookup_convc1_fwd_kernel(
         const float rb[12] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w};
 #pragma unroll
         for (int a = 0; a < N1; ++a)
-          s_tap[i & 1][a * N1 + (N1 - 1)][j] = ra[a] * w00 + ra[a + 1] * w01 + rb[a] * w10 + rb[a + 1] * w11;
+          s_tap[i & 1][a * N1 + (N1 - 1)][j] = blend4(ra[a], ra[a + 1], rb[a], rb[a + 1], w);
       }
     };
     if (dbg & 16) {
@@ -320,10 +214,11 @@ __global__ __launch_bounds__(NTF) void corr_lookup_convc1_fwd_kernel(
   // idled for the load latency in every group (26 us per launch, 28 % of the fp32 matrix peak).
   constexpr int WD = PCFA_LC_WD, NG = L * KG;
   f32x4 wring[WD][MTW];
-  int Ph[L], Ptw[L], Poff[L];     // all kernel-argument loads up front (the fences below would pin them per level)
+  int Ph[L], Pw[L], Ptw[L], Poff[L];   // all kernel-argument loads up front (the fences below would pin them per level)
 #pragma unroll
   for (int l = 0; l < L; ++l) {
     Ph[l] = P.h[l];
+    Pw[l] = P.w[l];
     Ptw[l] = P.tw[l];
     Poff[l] = P.off[l];
   }
@@ -333,8 +228,8 @@ __global__ __launch_bounds__(NTF) void corr_lookup_convc1_fwd_kernel(
   for (int lr = 0; lr < L; ++lr) {
     const int l = L - 1 - lr;
     FwdPieces g;
-    fwd_pieces(g, kx, ky, klive, l, kq, sub, Ph[l], Ptw[l], Poff[l], Pslab, Pzero);
-    const Origin oj = make_origin(cx, cy, l);
+    fwd_pieces(g, kx, ky, klive, l, kq, sub, Ph[l], Pw[l], Ptw[l], Poff[l], Pslab, Pzero);
+    const Origin oj = make_origin(cx, cy, l, R);
     fxs[l] = oj.fx;
     fys[l] = oj.fy;
 #pragma unroll
@@ -381,11 +276,10 @@ __global__ __launch_bounds__(NTF) void corr_lookup_convc1_fwd_kernel(
   };
   auto tap_out = [&](int i, int a, int b, const Rows& R) {   // tap (a, b) of stream level i from rows b, b + 1
     const int l = L - 1 - i;
-    const float fx = fxs[l], fy = fys[l];
-    const float w00 = (1.f - fx) * (1.f - fy), w01 = fx * (1.f - fy), w10 = (1.f - fx) * fy, w11 = fx * fy;
+    const BlendWeights w = blend_weights(fxs[l], fys[l]);
     const float t00 = R.a[a >> 2][a & 3], t01 = R.a[(a + 1) >> 2][(a + 1) & 3];
     const float t10 = R.b[a >> 2][a & 3], t11 = R.b[(a + 1) >> 2][(a + 1) & 3];
-    s_tap[i & 1][a * N1 + b][j] = t00 * w00 + t01 * w01 + t10 * w10 + t11 * w11;     // as corr_lookup_fwd_body
+    s_tap[i & 1][a * N1 + b][j] = blend4(t00, t01, t10, t11, w);
   };
   const int b8 = tid >> 5;
   static_assert(KG >= N1 + 1, "one tap of the row rides under each of the MFMA groups 1..9");
@@ -578,30 +472,18 @@ __global__ __launch_bounds__(NT) void corr_lookup_convc1_bwd_kernel(
     Poff[l] = P.off[l];
   }
   const int Pslab = P.slab, Pzero = P.zero;
-  struct LevelOrg { int x0, y0, ox; unsigned wB; };
+  struct LevelOrg { int x0, y0; unsigned wB; };   // clamped origin of query kq, bytes from the first slab to its level
   LevelOrg org[L];
   auto level_setup = [&](int l) {
-    const Origin o = make_origin(kx, ky, l);
-    const int th4 = ((Ph[l] + 3) >> 2) << 2;
-    org[l].x0 = min(max(o.x0, -16), 4 * Ptw[l]);
-    org[l].y0 = klive ? min(max(o.y0, -16), th4) : th4;
-    org[l].ox = org[l].x0 & 3;
-    org[l].wB = (unsigned)(Poff[l] + kq * Pslab) * 4u;
+    const Origin o = clamp_origin(make_origin(kx, ky, l, R), klive, Ph[l], Ptw[l]);
+    org[l] = LevelOrg{o.x0, o.y0, (unsigned)(Poff[l] + kq * Pslab) * 4u};
   };
-  auto piece_setup = [&](int l, int i) {   // as bwd_pieces, one piece
-    const int q = sub + 8 * i, rr = q >> 2, tx = q & 3;
-    const int hl = Ph[l], wl = Pw[l], tw = Ptw[l], ox = org[l].ox;
-    const int y = org[l].y0 + rr, gtx = (org[l].x0 >> 2) + tx;
-    const bool need = (unsigned)y < (unsigned)hl && (unsigned)gtx < (unsigned)tw && 4 * tx < ox + WIN;
-    const int c0 = 4 * tx - ox, gx0 = 4 * gtx;
-    int mask = need ? 16 : 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if ((unsigned)(c0 + e) < (unsigned)WIN && gx0 + e < wl) mask |= 1 << e;
-    pmask[l][i] = mask;
-    pgoff[l][i] = need ? org[l].wB + (((((unsigned)y >> 2) * (unsigned)tw + (unsigned)gtx) << 4) + (((unsigned)y & 3u) << 2)) * 4u
-                       : (unsigned)Pzero * 4u;
-    plds[l][i] = (unsigned)(kq * WS + rr * RS + 4 + 4 * tx - ox) * 4u;
+  auto piece_setup = [&](int l, int i) {   // the forward's ownership (fwd_pieces), one piece, with its texel mask
+    const int q = sub + 8 * i;
+    const Piece pc = piece_geometry(org[l].x0, org[l].y0, q >> 2, q & 3, Ph[l], Pw[l], Ptw[l], WIN);
+    pmask[l][i] = pc.mask;
+    pgoff[l][i] = pc.need() ? org[l].wB + pc.goff * 4u : (unsigned)Pzero * 4u;
+    plds[l][i] = ((unsigned)(kq * WS) + pc.lds) * 4u;
   };
   __builtin_amdgcn_sched_barrier(0);
   PCFA_LC_STAMP();   // 1: head done (the gradient tile's loads are in flight)
@@ -695,12 +577,11 @@ __global__ __launch_bounds__(NT) void corr_lookup_convc1_bwd_kernel(
   __syncthreads();   // d taps complete; the gradient tile is dead: its LDS becomes the window image
   PCFA_LC_STAMP();   // 3: GEMM done
 
-  // ---- per level: the lookup's transpose (corr_lookup_bwd_body with the tap gradients read from LDS) ----
+  // ---- per level: the lookup's transpose (window_grad_row / piece_add, the tap gradients read from LDS) ----
 #pragma unroll
   for (int l = 0; l < L; ++l) {
-    const Origin oj = make_origin(cx, cy, l);
-    const float fx = oj.fx, fy = oj.fy;
-    const float w00 = (1.f - fx) * (1.f - fy), w01 = fx * (1.f - fy), w10 = (1.f - fx) * fy, w11 = fx * fy;
+    const Origin oj = make_origin(cx, cy, l, R);
+    const BlendWeights w = blend_weights(oj.fx, oj.fy);
 #pragma unroll
     for (int pass = 0; pass < 2; ++pass) {
       const int row = pass == 0 ? (tid >> 5) : 8;
@@ -713,26 +594,12 @@ __global__ __launch_bounds__(NT) void corr_lookup_convc1_bwd_kernel(
       }
       float4* dst0 = reinterpret_cast<float4*>(&s_win[j * WS + row * RS + 4]);
       float d[NRD * 4];
-#pragma unroll
-      for (int c = 0; c < NRD * 4; ++c) {
-        float s = 0.f;
-        if (c < N1) s = gc[c] * w00;
-        if (c >= 1 && c <= N1) s = fmaf(gc[c - 1], w01, s);
-        if (c < N1) s = fmaf(gp[c], w10, s);
-        if (c >= 1 && c <= N1) s = fmaf(gp[c - 1], w11, s);
-        d[c] = s;
-      }
+      window_grad_row<N1, NRD>(gc, gp, w, d);
 #pragma unroll
       for (int i = 0; i < NRD; ++i) dst0[i] = make_float4(d[4 * i], d[4 * i + 1], d[4 * i + 2], d[4 * i + 3]);
       if (row == N1 - 1) {  // the owner of the last tap row also builds the window's last row
         float4* dst1 = reinterpret_cast<float4*>(&s_win[j * WS + (WIN - 1) * RS + 4]);
-#pragma unroll
-        for (int c = 0; c < NRD * 4; ++c) {
-          float s = 0.f;
-          if (c < N1) s = gc[c] * w10;
-          if (c >= 1 && c <= N1) s = fmaf(gc[c - 1], w11, s);
-          d[c] = s;
-        }
+        window_grad_last_row<N1, NRD>(gc, w, d);
 #pragma unroll
         for (int i = 0; i < NRD; ++i) dst1[i] = make_float4(d[4 * i], d[4 * i + 1], d[4 * i + 2], d[4 * i + 3]);
       }
@@ -742,14 +609,8 @@ __global__ __launch_bounds__(NT) void corr_lookup_convc1_bwd_kernel(
 #pragma unroll
     for (int i = 0; i < NPC; ++i) {
       const float* src = reinterpret_cast<const float*>(lds_bytes + plds[l][i]);
-      const float e0 = src[0], e1 = src[1], e2 = src[2], e3 = src[3];
-      const int m = pmask[l][i];
-      f32x4 t = v[l][i];
-      t.x += (m & 1) ? e0 : 0.f;
-      t.y += (m & 2) ? e1 : 0.f;
-      t.z += (m & 4) ? e2 : 0.f;
-      t.w += (m & 8) ? e3 : 0.f;
-      if (m & 16) store_piece(slab0, pgoff[l][i], t);
+      const f32x4 t = piece_add(v[l][i], src[0], src[1], src[2], src[3], pmask[l][i]);
+      if (pmask[l][i] & 16) store_piece(slab0, pgoff[l][i], t);
     }
     __syncthreads();   // image free for the next level
     PCFA_LC_STAMP();   // 4..7: level l scattered

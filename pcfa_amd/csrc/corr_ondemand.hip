@@ -116,26 +116,8 @@ T* at(void* ws, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(ws)
 template <typename T>
 const T* at(const void* ws, size_t off) { return reinterpret_cast<const T*>(static_cast<const char*>(ws) + off); }
 
-struct Origin {
-  int x0, y0;    // window origin (texels, level coordinates)
-  float fx, fy;  // shared bilinear fractions
-};
-
-// as corr_lookup.hip: coords / 2**l (exact power-of-two scaling), then floor / fraction
-__device__ __forceinline__ Origin make_origin(float cx, float cy, int level, int R) {
-  const float inv = 1.0f / (float)(1 << level);
-  const float xl = cx * inv, yl = cy * inv;
-  const float flx = floorf(xl), fly = floorf(yl);
-  Origin o;
-  o.fx = xl - flx;
-  o.fy = yl - fly;
-  o.x0 = (int)fminf(fmaxf(flx, -1.0e8f), 1.0e8f) - R;
-  o.y0 = (int)fminf(fmaxf(fly, -1.0e8f), 1.0e8f) - R;
-  return o;
-}
-
 }  // namespace
-#include "corr_ondemand_tiled.hpp"   // OdTile, the classification and the tile kernels
+#include "corr_ondemand_tiled.hpp"   // OdTile, the classification and the tile kernels (and corr_window.hpp)
 namespace {
 
 // ---- prepare -----------------------------------------------------------------------------------------------------------
@@ -258,9 +240,7 @@ __global__ __launch_bounds__(256) void od_fwd_kernel(OdLayout Lo, const float* _
       s_dot[wv][nb * 64 + lane] = acc[0] * inv_sqrt_d;
     }
     __syncthreads();
-    const float fx = o.fx, fy = o.fy;
-    const float w00 = (1.f - fx) * (1.f - fy), w01 = fx * (1.f - fy);
-    const float w10 = (1.f - fx) * fy, w11 = fx * fy;
+    const BlendWeights w = blend_weights(o.fx, o.fy);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int t = lane + 64 * h;
@@ -268,7 +248,7 @@ __global__ __launch_bounds__(256) void od_fwd_kernel(OdLayout Lo, const float* _
         const int a = t / N1, bb = t % N1;       // a: x offset, bb: y offset (channel a*(2r+1) + b)
         const float* c0 = &s_dot[wv][bb * WIN + a];
         const float* c1 = c0 + WIN;
-        s_out[t][qi] = c0[0] * w00 + c0[1] * w01 + c1[0] * w10 + c1[1] * w11;
+        s_out[t][qi] = blend4(c0[0], c0[1], c1[0], c1[1], w);
       }
     }
     __syncthreads();
@@ -322,9 +302,7 @@ __global__ __launch_bounds__(256) void od_bwd_kernel(OdLayout Lo, const float* _
       s_g[wv][t] = t < NT ? grad[((size_t)b * C + (size_t)l * NT + t) * Q + qc] : 0.f;
     }
     __syncthreads();
-    const float fx = o.fx, fy = o.fy;
-    const float w00 = (1.f - fx) * (1.f - fy), w01 = fx * (1.f - fy);
-    const float w10 = (1.f - fx) * fy, w11 = fx * fy;
+    const BlendWeights w = blend_weights(o.fx, o.fy);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int p = lane + 64 * h;
@@ -333,10 +311,10 @@ __global__ __launch_bounds__(256) void od_bwd_kernel(OdLayout Lo, const float* _
         const float* G = s_g[wv];
         // tap (a, bb) blends positions (a, bb) w00, (a+1, bb) w01, (a, bb+1) w10, (a+1, bb+1) w11
         float dc = 0.f;
-        if (i < N1 && j < N1) dc += w00 * G[i * N1 + j];
-        if (i >= 1 && j < N1) dc += w01 * G[(i - 1) * N1 + j];
-        if (i < N1 && j >= 1) dc += w10 * G[i * N1 + j - 1];
-        if (i >= 1 && j >= 1) dc += w11 * G[(i - 1) * N1 + j - 1];
+        if (i < N1 && j < N1) dc += w.w00 * G[i * N1 + j];
+        if (i >= 1 && j < N1) dc += w.w01 * G[(i - 1) * N1 + j];
+        if (i < N1 && j >= 1) dc += w.w10 * G[i * N1 + j - 1];
+        if (i >= 1 && j >= 1) dc += w.w11 * G[(i - 1) * N1 + j - 1];
         const int X = o.x0 + i, Y = o.y0 + j;
         const bool ok = X >= 0 && X < wl && Y >= 0 && Y < hl;
         s_dc[wv][p] = ok ? dc * inv_sqrt_d : 0.f;

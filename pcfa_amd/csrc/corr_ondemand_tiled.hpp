@@ -1,7 +1,8 @@
 // The tiled execution of the on-demand correlation lookup (Config.ondemand_lookup = "tiled"); included by
-// corr_ondemand.hip after OdLayout / make_origin, whose header comment states the decomposition and the budgets.
+// corr_ondemand.hip after OdLayout, whose header comment states the decomposition and the budgets.
 #pragma once
-#include "gemm_tile.hpp"   // f32x16 and the C/D register map of the 32x32 MFMA
+#include "corr_window.hpp"   // Origin / make_origin, the blend
+#include "gemm_tile.hpp"     // f32x16 and the C/D register map of the 32x32 MFMA
 
 namespace {
 
@@ -176,14 +177,12 @@ __global__ __launch_bounds__(256) void od_fwd_tile_kernel(OdLayout Lo, const flo
     const int tap = i / OD_TQ, qi = i % OD_TQ;
     const int y = ty0 + qi / OD_TW, x = tx0 + qi % OD_TW;
     if (y >= Lo.H || x >= Lo.W) continue;
-    const float fx = s_q[qi].fx, fy = s_q[qi].fy;
-    const float w00 = (1.f - fx) * (1.f - fy), w01 = fx * (1.f - fy);
-    const float w10 = (1.f - fx) * fy, w11 = fx * fy;
+    const BlendWeights w = blend_weights(s_q[qi].fx, s_q[qi].fy);
     const int a = tap / N1, bb = tap % N1;
     const float* c0 = &s_win[qi][bb * WIN + a];
     const float* c1 = c0 + WIN;
     out[((size_t)b * C + (size_t)l * NT + tap) * Q + (size_t)y * Lo.W + x] =
-        c0[0] * w00 + c0[1] * w01 + c1[0] * w10 + c1[1] * w11;
+        blend4(c0[0], c0[1], c1[0], c1[1], w);
   }
 }
 
@@ -286,14 +285,12 @@ __global__ __launch_bounds__(256) void od_bwd_tile_kernel(OdLayout Lo, const flo
             const int i = X - tq.qx0, j = Y - tq.qy0;
             float dc = 0.f;
             if (inmap && i >= 0 && i < WIN && j >= 0 && j < WIN) {
-              const float fx = tq.fx, fy = tq.fy;
-              const float w00 = (1.f - fx) * (1.f - fy), w01 = fx * (1.f - fy);
-              const float w10 = (1.f - fx) * fy, w11 = fx * fy;
+              const BlendWeights w = blend_weights(tq.fx, tq.fy);
               const float* G = s_g[qi];
-              if (i < N1 && j < N1) dc += w00 * G[i * N1 + j];
-              if (i >= 1 && j < N1) dc += w01 * G[(i - 1) * N1 + j];
-              if (i < N1 && j >= 1) dc += w10 * G[i * N1 + j - 1];
-              if (i >= 1 && j >= 1) dc += w11 * G[(i - 1) * N1 + j - 1];
+              if (i < N1 && j < N1) dc += w.w00 * G[i * N1 + j];
+              if (i >= 1 && j < N1) dc += w.w01 * G[(i - 1) * N1 + j];
+              if (i < N1 && j >= 1) dc += w.w10 * G[i * N1 + j - 1];
+              if (i >= 1 && j >= 1) dc += w.w11 * G[(i - 1) * N1 + j - 1];
               dc *= inv_sqrt_d;
             }
             s_dc[qi * OD_LDC + pp] = dc;

@@ -15,7 +15,7 @@
 // GEMM core: 128x128x16 block tile, 4 waves (2x2), each wave 2x2 tiles of
 // v_mfma_f32_32x32x2_f32 (exact fp32, k-ordered fma chain), LDS double buffer
 // fed by register prefetch.
-#include "common.hpp"
+#include "corr_window.hpp"   // window_texel: the texel a lookup window starts from
 #include "gemm_tile.hpp"   // block tile, PoolArgs, the epilogues, the split-K reduction
 
 namespace {
@@ -538,9 +538,10 @@ struct CoordList {
 };
 
 // Which part of dpyr can be non-zero?  Every lookup's backward adds into the (2r+2)^2 texels around
-// (cx / 2^l, cy / 2^l) of its queries (corr_lookup.hip); with the coordinates of all lookups of this backward pass the
-// rows a query row can have touched at level l are  floor(min cy / 2^l) - r - 1 .. floor(max cy / 2^l) + r + 2  (one
-// texel of slack on either side).  In the 4x4-tiled slab a range of tile rows is a contiguous range of columns, so
+// (cx / 2^l, cy / 2^l) of its queries, from window_texel(c, l) - r on (corr_window.hpp: the lookups' own floor and
+// clamp; it is monotone in c); with the coordinates of all lookups of this backward pass the rows a query row can have
+// touched at level l are  window_texel(min cy) - r - 1 .. window_texel(max cy) + r + 2  (one texel of slack on either
+// side: the tables' own rule).  In the 4x4-tiled slab a range of tile rows is a contiguous range of columns, so
 //   segA[b][query block j] : per level, the slab-column segment the 128 queries of block j can have touched
 //                            (K segments of  dfmap1 = f2ext . dpyr^T);
 //   segB[b][column block j]: the range of query rows that can have touched the block's slab columns
@@ -580,11 +581,9 @@ __global__ __launch_bounds__(256) void corr_window_rows_kernel(CoordList cl, int
     const int l = threadIdx.x;
     lo = fminf(fminf(s_lo[0], s_lo[1]), fminf(s_lo[2], s_lo[3]));
     hi = fmaxf(fmaxf(s_hi[0], s_hi[1]), fmaxf(s_hi[2], s_hi[3]));
-    const float inv = 1.0f / (float)(1 << l);
-    const float flo = fminf(fmaxf(floorf(lo * inv), -1.0e8f), 1.0e8f), fhi = fminf(fmaxf(floorf(hi * inv), -1.0e8f), 1.0e8f);
     int* o = rows + (((long long)b * P.L + l) * H + qy) * 2;
-    o[0] = max((int)flo - r - 1, 0);
-    o[1] = min((int)fhi + r + 2, P.h[l] - 1);     // (may be < the low end: nothing touched)
+    o[0] = max(window_texel(lo, l) - r - 1, 0);
+    o[1] = min(window_texel(hi, l) + r + 2, P.h[l] - 1);     // (may be < the low end: nothing touched)
   }
 }
 
@@ -688,13 +687,11 @@ __global__ __launch_bounds__(256) void corr_window_runs_kernel(CoordList cl, int
     if (bad) { xlo = ylo = -3.0e38f; xhi = yhi = 3.0e38f; }
     if (x < W && x % RUN == 0)
       for (int l = 0; l < P.L; ++l) {
-        const float inv = 1.0f / (float)(1 << l);
-        const auto tex = [&](float v) { return (int)fminf(fmaxf(floorf(v * inv), -1.0e8f), 1.0e8f); };
         int4 t;
-        t.x = max(tex(xlo) - r - 1, 0);
-        t.y = min(tex(xhi) + r + 2, P.w[l] - 1);
-        t.z = max(tex(ylo) - r - 1, 0);
-        t.w = min(tex(yhi) + r + 2, P.h[l] - 1);
+        t.x = max(window_texel(xlo, l) - r - 1, 0);
+        t.y = min(window_texel(xhi, l) + r + 2, P.w[l] - 1);
+        t.z = max(window_texel(ylo, l) - r - 1, 0);
+        t.w = min(window_texel(yhi, l) + r + 2, P.h[l] - 1);
         *reinterpret_cast<int4*>(runs + ((((long long)b * P.L + l) * H + qy) * NR + x / RUN) * 4) = t;
       }
   }
@@ -713,11 +710,9 @@ __global__ __launch_bounds__(256) void corr_window_runs_kernel(CoordList cl, int
     const int l = threadIdx.x;
     rlo = fminf(fminf(s_lo[0], s_lo[1]), fminf(s_lo[2], s_lo[3]));
     rhi = fmaxf(fmaxf(s_hi[0], s_hi[1]), fmaxf(s_hi[2], s_hi[3]));
-    const float inv = 1.0f / (float)(1 << l);
-    const float flo = fminf(fmaxf(floorf(rlo * inv), -1.0e8f), 1.0e8f), fhi = fminf(fmaxf(floorf(rhi * inv), -1.0e8f), 1.0e8f);
     int* o = rows + (((long long)b * P.L + l) * H + qy) * 2;
-    o[0] = max((int)flo - r - 1, 0);
-    o[1] = min((int)fhi + r + 2, P.h[l] - 1);
+    o[0] = max(window_texel(rlo, l) - r - 1, 0);
+    o[1] = min(window_texel(rhi, l) + r + 2, P.h[l] - 1);
   }
 }
 

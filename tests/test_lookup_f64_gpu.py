@@ -19,8 +19,8 @@ and 256 + 9 = 265 (fused backward).  Ratios and worst classes are recorded as ju
 junit_family=xunit1).
 
 Non-finite coordinates: make_origin clamps the floor to +-1e8 before the conversion to int (fmaxf / fminf return the other
-operand for NaN) and the integer origin is then clamped to [-16, 4 tw] x [-16, th4] in all five statements of the window
-geometry (make_piece via Block::init, level_geometry, fwd_pieces, bwd_pieces, piece_setup via level_setup), so every address
+operand for NaN) and the integer origin is then clamped to [-16, 4 tw] x [-16, th4] by clamp_origin (csrc/corr_window.hpp,
+the one statement behind make_piece via Block::init, fwd_pieces and piece_setup via level_setup), so every address
 is in range for any float; such a window has no piece inside its level.  The `nonfinite` case asserts that every other query
 passes the gates, that the poisoned queries' dpyr slabs are bit-unchanged and that the fences hold; what the poisoned queries'
 own forward outputs hold (NaN: 0 x NaN) is recorded, not asserted.
