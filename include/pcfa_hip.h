@@ -669,8 +669,9 @@ PCFA_API int pcfa_relu_bwd2(const float* out, const float* out2, const float* gr
 
 /* act(conv2d(x, w, bias, stride=1, padding=ksize/2)) for Cin <= 4 input channels, forward only: convf1 of the
  * motion encoder (models/raft/update.py:79-101, Conv2d(2, 128, 7, padding=3) + ReLU on the detached flow).
- * x: [B][Cin][H][W]; w: [N][Cin][k][k]; out: [B][N][H][W].  Supported (Cin, ksize): (2,7) (1,7) (2,5) (2,3);
- * anything else returns PCFA_ERR_UNSUPPORTED (the caller keeps the library convolution). */
+ * x: [B][Cin][H][W]; w: [N][Cin][k][k], 16-B aligned (it is read in 16-B pieces; PCFA_ERR_INVALID_ARG otherwise);
+ * out: [B][N][H][W].  Supported (Cin, ksize): (2,7) (1,7) (2,5) (2,3); anything else, and a shape whose weights and
+ * input range exceed 150 KB of LDS, returns PCFA_ERR_UNSUPPORTED (the caller keeps the library convolution). */
 PCFA_API int pcfa_conv_fewin_fwd(const float* x, const float* w, const float* bias, float* out, int B, int Cin, int N,
                                  int H, int W, int ksize, int relu, void* stream);
 /* The same layer with the frozen weight packed once in MFMA operand order (pcfa_conv_fewin_packed_floats(Cin, N, ksize)

@@ -339,7 +339,8 @@ int launch_fewin(const float* x, const float* w, const float* bias, float* out, 
 
 extern "C" int pcfa_conv_fewin_fwd(const float* x, const float* w, const float* bias, float* out, int B, int Cin,
                                    int N, int H, int W, int ksize, int relu, void* stream) {
-  if (!x || !w || !out || B < 1 || N < 1 || H < 1 || W < 1) return PCFA_ERR_INVALID_ARG;
+  if (!x || !w || !out || B < 1 || N < 1 || H < 1 || W < 1 || (reinterpret_cast<uintptr_t>(w) & 15))
+    return PCFA_ERR_INVALID_ARG;  // the kernel stages w in 16-B pieces
   hipStream_t s = (hipStream_t)stream;
   if (ksize == 7 && Cin == 2) return launch_fewin<2, 7>(x, w, bias, out, B, N, H, W, relu, s);
   if (ksize == 7 && Cin == 1) return launch_fewin<1, 7>(x, w, bias, out, B, N, H, W, relu, s);
