@@ -418,6 +418,41 @@ PCFA_API int pcfa_fgsm_step(float* x1, float* x2, const float* g1, const float* 
                             float* d1, float* d2, float epsilon, int joint, long long n, void* stream);
 PCFA_API int pcfa_fgsm_step_max_threads(void);
 
+/* One projected-gradient iteration under the averaged-L2 budget on both images, in place (attack_FGSM.pgd_l2_attack_step
+ * is the same arithmetic in torch).  n floats per array, N = 2n; epsilon and delta_bound enter as the doubles of their
+ * fp32 values:
+ *   joint == 1:  g1 = g2 = 0.5f * (g1 + g2)     (the fp32 sum is rounded first, as in pcfa_fgsm_step)
+ *   G   = sum g1^2 + sum g2^2                   double (an fp32 square is exact there), fixed order
+ *   a   = (float)(epsilon * sqrt(N / G))        in double, rounded once: the move has averaged L2 length epsilon;
+ *                                               a = 0 where G is 0, NaN or Inf, or where the rounded a is not finite:
+ *                                               a * g_i is then taken as 0 whatever g_i is (nothing moves or turns NaN)
+ *   y_i = clamp(x_i - a * g_i, 0, 1)            product rounded, then the difference (no fma); the clamp keeps NaN
+ *   e_i = y_i - img_i
+ *   E   = sum e1^2 + sum e2^2                   double, same order;  r = sqrt(E / N)
+ *   r > delta_bound and s = (float)(delta_bound / r) != 1:
+ *         x_i <- clamp(img_i + s * e_i, 0, 1)   product rounded, then the sum (no fma)
+ *         d_i  = x_i - img_i                    (from the updated x_i)
+ *   otherwise (a non-finite E included) s = 1:  x_i <- y_i,  d_i = e_i   bit for bit
+ * Three launches on `stream` -- partials of G; the step with the partials of E; the projection, which returns at once
+ * where s == 1 -- with no atomics, no memset and no host read, so the call can be captured.  The grid, the partials and
+ * the order of every sum depend on n alone: element i belongs to quad i / 4, quad q to thread q % (workgroups * 256),
+ * a thread adds its squares in index order (g1 before g2), a wave by shuffles, the workgroup's four waves in wave order,
+ * the partials lane-strided and then likewise; every workgroup forms the same a and s.  16-byte accesses where all eight
+ * array pointers are 16-byte aligned, scalar ones otherwise (ONE decision for all three launches; n need not be a multiple
+ * of 4); both give the same bits.  g1 / g2 / img1 / img2 are only read.
+ * workspace: pcfa_pgd_l2_workspace_bytes() bytes, 8-byte aligned, caller-owned, uninitialised, one call in flight per
+ * workspace.  After a call its first four doubles are G, a, E, s; behind them lie the partials, of which every slot that
+ * is read was written by the same call.  pcfa_pgd_l2_max_threads(): the most threads one launch starts; each handles one
+ * quad per trip of its grid-stride loop.
+ * A NULL or misaligned pointer, n < 0, joint outside {0, 1}, or an epsilon or delta_bound that is not positive and finite
+ * is PCFA_ERR_INVALID_ARG and launches nothing; n == 0 is success and writes nothing.  (Added without a change of
+ * PCFA_ABI_VERSION, like the other additive entries.) */
+PCFA_API size_t pcfa_pgd_l2_workspace_bytes(void);
+PCFA_API int pcfa_pgd_l2_max_threads(void);
+PCFA_API int pcfa_pgd_l2_step(float* x1, float* x2, const float* g1, const float* g2, const float* img1, const float* img2,
+                              float* d1, float* d2, float epsilon, float delta_bound, int joint, long long n,
+                              void* workspace, void* stream);
+
 /* Bit digest of a buffer of 32-bit words (pcfa_amd/trace.py: which operator's bits differ first between two runs; nothing
  * in the default attack path calls it).  Word k of x has the global index i = index0 + k and the bit pattern w_i as an
  * unsigned 32-bit value; the call OVERWRITES out4 with four 64-bit values, each taken mod 2^64:

@@ -94,6 +94,9 @@ SIGNATURES = {
     "pcfa_extract_deltas_joint_bwd": (c_int, [_P, _P, _P, _P, _P, c_longlong, _P]),
     "pcfa_fgsm_step": (c_int, [_P] * 8 + [c_float, c_int, c_longlong, _P]),
     "pcfa_fgsm_step_max_threads": (c_int, []),
+    "pcfa_pgd_l2_workspace_bytes": (c_size_t, []),
+    "pcfa_pgd_l2_max_threads": (c_int, []),
+    "pcfa_pgd_l2_step": (c_int, [_P] * 8 + [c_float, c_float, c_int, c_longlong, _P, _P]),
     "pcfa_digest_workspace_bytes": (c_size_t, []),
     "pcfa_digest_words": (c_int, [_P, c_ulonglong, c_ulonglong, _P, _P, _P]),
     "pcfa_flow_loss_workspace_bytes": (c_size_t, []),

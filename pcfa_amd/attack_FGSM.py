@@ -4,6 +4,8 @@ One iteration = 1 backward + a signed-gradient step of size --epsilon with the i
 moved images; `--joint_perturbation` averages the two image gradients before taking the sign.
 
     fgsm_attack_step     attack_FGSM.py:21-56     (torch; the CPU port and the arithmetic the kernel is tested against)
+    pgd_l2_attack_step   (no counterpart)         `--step_norm l2`: a step of averaged L2 length --epsilon, then the
+                                                  projection onto two_norm_avg_delta <= --delta_bound (torch; the CPU port)
     FgsmAttack           attack_FGSM.py:150-254   one pair: static buffers, captured forward / backward, `step()`
     fgsm_attack          FgsmAttack + args.steps x step()
     attack               attack_FGSM.py:59-308    every pair of a dataset, `--pairs_in_flight`, artefacts, rank sharding
@@ -13,9 +15,11 @@ per shape into two hipGraphs (graphed.SplitGraphedStep), the signed step and the
 (ops.fgsm_step, in place on the static images), the six per-iteration metrics of the reference (attack_FGSM.py:199-241) are
 computed inside the forward graph and collected in a device buffer that is read back once after the last iteration.  Nothing
 in `step()` allocates or waits for the GPU, so several pairs can be in flight (attack_PCFA.PairsInFlight)."""
+import math
 import os
 import time
 
+import numpy as np
 import torch
 
 from . import config, graph_sets, ops, sharding
@@ -41,6 +45,59 @@ def fgsm_attack_step(image1, image2, epsilon, image1_grad, image2_grad, image_mi
     return p1, p2
 
 
+def _f32(v):
+    """The fp32 value nearest to the Python float v, as a Python float (inf past the range)."""
+    with np.errstate(over="ignore"):
+        return float(np.float32(v))
+
+
+def _sum_squares_f64(a, b):
+    return float(a.double().square().sum() + b.double().square().sum())
+
+
+def pgd_l2_attack_step(x1, x2, image1_grad, image2_grad, image1, image2, epsilon, delta_bound, common_perturb=False):
+    """One projected-gradient iteration under PCFA's budget (`--step_norm l2`; the reference has no projection).
+    This is the arithmetic ops.pgd_l2_step implements (include/pcfa_hip.h) and the CPU port's path.  n floats per image,
+    N = 2n; epsilon and delta_bound enter as their fp32 values, as the kernel receives them:
+
+        joint        g1 = g2 = 0.5f * (g1 + g2), the fp32 sum rounded first as in fgsm_attack_step
+        G            sum g1^2 + sum g2^2 in double (here in torch's order, in the kernel in the order the header states)
+        a            fp32(epsilon * sqrt(N / G)), evaluated in double and rounded once: the move a * g has averaged L2
+                     length epsilon, what a signed step of size epsilon has.  a = 0 where G is 0, NaN or Inf (or the
+                     rounded a is not finite): then nothing moves -- the product a * g is not formed -- and nothing turns NaN
+        y_i, e_i     clamp(x_i - a * g_i, 0, 1), product rounded, then the difference;  e_i = y_i - image_i
+        E, r         sum e1^2 + sum e2^2 in double;  r = sqrt(E / N) = two_norm_avg_delta(e1, e2)
+        r > b        s = fp32(b / r);  x_i <- clamp(image_i + s * e_i, 0, 1), product rounded, then the sum;
+                     d_i = x_i - image_i from the updated x_i
+        otherwise    (also: E not finite, or a quotient that rounds to 1)  s = 1, x_i <- y_i, d_i = e_i as they are
+
+    Returns (x1', x2', d1, d2, (G, a, E, s)).  Reads its scalars on the host: not for a captured loop."""
+    eps, bound = _f32(epsilon), _f32(delta_bound)
+    g1, g2 = image1_grad, image2_grad
+    if common_perturb:
+        g1 = g2 = 0.5 * (g1 + g2)
+    n_total = float(g1.numel() + g2.numel())
+    G = _sum_squares_f64(g1, g2)
+    a = _f32(eps * math.sqrt(n_total / G)) if 0. < G < math.inf else 0.
+    if not math.isfinite(a):
+        a = 0.
+    if a == 0.:
+        y1, y2 = torch.clamp(x1, 0., 1.), torch.clamp(x2, 0., 1.)
+    else:
+        y1, y2 = torch.clamp(x1 - a * g1, 0., 1.), torch.clamp(x2 - a * g2, 0., 1.)
+    e1, e2 = y1 - image1, y2 - image2
+    E = _sum_squares_f64(e1, e2)
+    s = 1.
+    if E < math.inf:
+        r = math.sqrt(E / n_total)
+        if r > bound:
+            s = _f32(bound / r)
+    if s == 1.:
+        return y1, y2, e1, e2, (G, a, E, s)
+    p1, p2 = torch.clamp(image1 + s * e1, 0., 1.), torch.clamp(image2 + s * e2, 0., 1.)
+    return p1, p2, p1 - image1, p2 - image2, (G, a, E, s)
+
+
 class FgsmAttack:
     """Everything the reference's loop holds for ONE image pair (attack_FGSM.py:150-254) and `step()`, one iteration:
     backward at x_i, signed step, forward at x_{i+1}, metrics.  `fgsm_attack` is `FgsmAttack(...)` + args.steps x `step()`.
@@ -49,10 +106,12 @@ class FgsmAttack:
     that has the step kernel) forward and loss + backward are replayed from hipGraphs captured once per key and kept per model
     for the next pair of that key (`reuse_graphs`, default Config.reuse_pair_graphs), the step is one launch of ops.fgsm_step,
     and the metrics go to a device buffer: `step()` neither allocates nor synchronises.  If capture fails a warning is logged
-    and the eager loop -- the same kernels in the same order -- runs.  `history` (one dict per iteration, the reference's
-    names) and `result()` read the buffer back, once.  Since `step()` does not wait, a caller that moves a lane to another
-    stream reads a result (or synchronises) first: a lane's scratch buffers belong to one stream-ordered sequence of launches
-    (ops.core); `fgsm_attack` and PairsInFlight.run both end with such a wait."""
+    and the eager loop -- the same kernels in the same order -- runs.  With `args.step_norm == "l2"` the step is
+    ops.pgd_l2_step instead (pgd_l2_attack_step: three launches, outside the graphs like the signed step, no host read) and
+    every iterate satisfies two_norm_avg_delta <= args.delta_bound; nothing else in the loop differs.  `history` (one dict
+    per iteration, the reference's names) and `result()` read the buffer back, once.  Since `step()` does not wait, a caller
+    that moves a lane to another stream reads a result (or synchronises) first: a lane's scratch buffers belong to one
+    stream-ordered sequence of launches (ops.core); `fgsm_attack` and PairsInFlight.run both end with such a wait."""
 
     def __init__(self, model, image1, image2, flow, batch, device, has_gt, args, use_graph=None, reuse_graphs=None):
         self.model, self.args, self.device, self.batch, self.has_gt = model, args, device, batch, has_gt
@@ -60,7 +119,19 @@ class FgsmAttack:
             reuse_graphs = config.cfg(model).reuse_pair_graphs
         self.reuse_graphs = reuse_graphs
         self.joint = bool(args.joint_perturbation)
-        self.has_step_kernel = hasattr(ops.get(), "fgsm_step")   # the CPU port's table has none: torch fallback
+        self.step_norm = getattr(args, "step_norm", "sign")
+        if self.step_norm not in ("sign", "l2"):
+            raise ValueError("--step_norm is 'sign' or 'l2', got %r" % (self.step_norm,))
+        self._take_step = self._l2_step if self.step_norm == "l2" else self._signed_step
+        # the CPU port's table has neither step kernel: torch fallback
+        self.has_step_kernel = hasattr(ops.get(), "pgd_l2_step" if self.step_norm == "l2" else "fgsm_step")
+        self.delta_bound = None    # the budget of the l2 step; the signed step has none
+        if self.step_norm == "l2":
+            self.delta_bound = float(args.delta_bound)
+            if not (0 < self.delta_bound < math.inf and 0 < args.epsilon < math.inf):
+                raise ValueError("--step_norm l2 needs a positive, finite --epsilon and --delta_bound, got %r and %r"
+                                 % (args.epsilon, args.delta_bound))
+            logging.log_param("delta_bound", self.delta_bound)
         image1, image2 = image1.to(device), image2.to(device)
         self.flow_gt = flow.to(device) if (flow is not None and has_gt) else None
         if not ownutilities.model_takes_unit_input(args.net):
@@ -73,7 +144,7 @@ class FgsmAttack:
         use_graph = bool(use_graph) and self.has_step_kernel and torch.device(device).type == "cuda"
         # (the un-padded shape is part of the key: it is the shape of the flow, the target and the metrics' operands)
         self.graph_key = (args.net, tuple(image1.shape), raw_shape, args.loss, self.joint, float(args.epsilon), args.target,
-                          str(device), ops.core.current_lane())
+                          self.step_norm, self.delta_bound, str(device), ops.core.current_lane())
         self.graphed = None
         self.retired = False
         self.steps_done = 0
@@ -208,6 +279,19 @@ class FgsmAttack:
             self.x1.copy_(p1)
             self.x2.copy_(p2)
 
+    def _l2_step(self, g1, g2):
+        if self.has_step_kernel:
+            ops.get().pgd_l2_step(self.x1, self.x2, g1.contiguous(), g2.contiguous(), self.image1, self.image2, self.delta1,
+                                  self.delta2, self.args.epsilon, self.delta_bound, self.joint)
+            self.step_launches += 1
+            return
+        with torch.no_grad():    # operator tables without the kernel (the CPU port)
+            p1, p2, d1, d2, _ = pgd_l2_attack_step(self.x1, self.x2, g1, g2, self.image1, self.image2, self.args.epsilon,
+                                                   self.delta_bound, common_perturb=self.joint)
+            self.delta1, self.delta2 = d1, d2
+            self.x1.copy_(p1)
+            self.x2.copy_(p2)
+
     # ---- one iteration (attack_FGSM.py:199-241) -----------------------------------------------------------------
     def step(self):
         self._check_live()
@@ -216,14 +300,14 @@ class FgsmAttack:
             self._hist = torch.cat([self._hist, torch.empty_like(self._hist)])
         if self.graphed is not None:
             g1, g2 = self.graphed.backward()
-            self._signed_step(g1, g2)
+            self._take_step(g1, g2)
             _, row = self.graphed.forward()
         else:
             loss = self._loss(self.flow_pred)
             self.model.zero_grad()
             self.x1.grad = self.x2.grad = None
             loss.backward()
-            self._signed_step(self.x1.grad.data, self.x2.grad.data)
+            self._take_step(self.x1.grad.data, self.x2.grad.data)
             self.flow_pred, row = self._forward_with_metrics()
         self._hist[k].copy_(row)
         self.steps_done = k + 1

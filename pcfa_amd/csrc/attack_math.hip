@@ -873,3 +873,249 @@ extern "C" int pcfa_fgsm_step(float* x1, float* x2, const float* g1, const float
   PCFA_LAUNCH_CHECK();
   return PCFA_OK;
 }
+
+// ---------------------------------------------------------------- projected-gradient step under the averaged-L2 budget
+// attack_FGSM.pgd_l2_attack_step in three launches on one stream (include/pcfa_hip.h states the arithmetic):
+//   1. pgd_l2_gsq_kernel    workgroup partials of G = sum g1^2 + sum g2^2
+//   2. pgd_l2_step_kernel   every workgroup adds the G partials (the same order everywhere, so the same a), writes
+//                           y = clamp(x - a g, 0, 1) and e = y - img into x and d, and its partial of E = sum e^2
+//   3. pgd_l2_project_kernel  every workgroup adds the E partials; s == 1 returns at once, else x and d are rewritten
+// No atomics, no memset, nothing read by the host.  An element belongs to the quad q = i / 4 and a quad to the thread
+// q % (workgroups * 256) whether the accesses are 16-byte ones or scalar ones, so the grid, the partials and every sum
+// depend on n alone.  Sums are double: a thread adds its elements' squares (exact in double) in index order, g1 before
+// g2; a wave adds by shuffles; the four waves go through LDS and are added in wave order; the partials are added
+// lane-strided, then the same way.  Every partial slot a launch reads was written by the launch before it.
+namespace {
+
+constexpr int PGD_THREADS = 256;
+constexpr int PGD_MAX_BLOCKS = 1024;
+constexpr int PGD_SCALARS = 4;   // workspace doubles 0..3: G, a, E, s; then PGD_MAX_BLOCKS partials of G and as many of E
+
+// One fp32 rounding each, never fused: the compiler contracts a * b + c into an fma by default and the *_rn intrinsics
+// are plain operators to it (fgsm_one can live with that: its products are exact).  The pragma takes the `contract` flag
+// off these operations, and an operation without the flag is not fused after inlining either.
+__device__ __forceinline__ float pgd_mul(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float pgd_add(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ float pgd_sub(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+
+__device__ __forceinline__ double pgd_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+
+// the workgroup's sum, in every thread
+__device__ __forceinline__ double pgd_block_sum(double v, double* smem /*[4]*/) {
+  const double w = pgd_wave_sum(v);
+  if ((threadIdx.x & 63) == 0) smem[threadIdx.x >> 6] = w;
+  __syncthreads();
+  return ((smem[0] + smem[1]) + smem[2]) + smem[3];
+}
+
+__device__ __forceinline__ double pgd_sum_partials(const double* __restrict__ partial, int count, double* smem) {
+  double v = 0.;
+  for (int i = threadIdx.x; i < count; i += PGD_THREADS) v += partial[i];
+  return pgd_block_sum(v, smem);
+}
+
+// quad q of an array of n floats; elements past n read as 0 (they add nothing to a sum) and are never stored
+template <bool VEC>
+__device__ __forceinline__ float4 pgd_load(const float* p, long long q, long long n) {
+  const long long i = q << 2;
+  if (VEC && i + 3 < n) return reinterpret_cast<const float4*>(p)[q];
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (i < n) v.x = p[i];
+  if (i + 1 < n) v.y = p[i + 1];
+  if (i + 2 < n) v.z = p[i + 2];
+  if (i + 3 < n) v.w = p[i + 3];
+  return v;
+}
+
+template <bool VEC>
+__device__ __forceinline__ void pgd_store(float* p, long long q, long long n, float4 v) {
+  const long long i = q << 2;
+  if (VEC && i + 3 < n) {
+    reinterpret_cast<float4*>(p)[q] = v;
+    return;
+  }
+  if (i < n) p[i] = v.x;
+  if (i + 1 < n) p[i + 1] = v.y;
+  if (i + 2 < n) p[i + 2] = v.z;
+  if (i + 3 < n) p[i + 3] = v.w;
+}
+
+// joint: both images move along 0.5f * (g1 + g2), the fp32 sum rounded first as in fgsm_one
+__device__ __forceinline__ void pgd_grad(float& g1, float& g2, int joint) {
+  if (joint) g1 = g2 = pgd_mul(0.5f, pgd_add(g1, g2));
+}
+
+__device__ __forceinline__ double pgd_sq(double acc, float v1, float v2) {
+  acc += (double)v1 * (double)v1;
+  acc += (double)v2 * (double)v2;
+  return acc;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(PGD_THREADS) void pgd_l2_gsq_kernel(const float* __restrict__ g1, const float* __restrict__ g2,
+                                                                 int joint, long long n, double* __restrict__ partial_g) {
+  __shared__ double smem[4];
+  const long long nq = (n + 3) >> 2, stride = (long long)gridDim.x * PGD_THREADS;
+  double acc = 0.;
+  for (long long q = (long long)blockIdx.x * PGD_THREADS + threadIdx.x; q < nq; q += stride) {
+    float4 a = pgd_load<VEC>(g1, q, n), b = pgd_load<VEC>(g2, q, n);
+    pgd_grad(a.x, b.x, joint);
+    pgd_grad(a.y, b.y, joint);
+    pgd_grad(a.z, b.z, joint);
+    pgd_grad(a.w, b.w, joint);
+    acc = pgd_sq(pgd_sq(pgd_sq(pgd_sq(acc, a.x, b.x), a.y, b.y), a.z, b.z), a.w, b.w);
+  }
+  const double sum = pgd_block_sum(acc, smem);
+  if (threadIdx.x == 0) partial_g[blockIdx.x] = sum;
+}
+
+// y = clamp(x - a * g, 0, 1): the product is rounded, then the difference (no fma); e = y - img.  a == 0 moves nothing:
+// the product is not formed (0 * Inf and 0 * NaN would be NaN)
+__device__ __forceinline__ void pgd_move(float x, float g, float img, float a, float& y, float& e) {
+  y = fgsm_clamp01(pgd_sub(x, a == 0.f ? 0.f : pgd_mul(a, g)));
+  e = pgd_sub(y, img);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(PGD_THREADS) void pgd_l2_step_kernel(float* x1, float* x2, const float* __restrict__ g1,
+                                                                  const float* __restrict__ g2,
+                                                                  const float* __restrict__ img1,
+                                                                  const float* __restrict__ img2, float* __restrict__ d1,
+                                                                  float* __restrict__ d2, double epsilon, int joint,
+                                                                  long long n, double* __restrict__ ws) {
+  __shared__ double smem_g[4], smem_e[4];
+  const double G = pgd_sum_partials(ws + PGD_SCALARS, gridDim.x, smem_g);
+  // a = 0 where the gradient has no length to scale by (G is 0, NaN or Inf) or the factor has no fp32 value
+  float a = 0.f;
+  if (G > 0. && G < __builtin_inf()) {
+    a = (float)(epsilon * sqrt((double)(2 * n) / G));
+    if (!(a < __builtin_inff())) a = 0.f;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    ws[0] = G;
+    ws[1] = (double)a;
+  }
+  const long long nq = (n + 3) >> 2, stride = (long long)gridDim.x * PGD_THREADS;
+  double acc = 0.;
+  for (long long q = (long long)blockIdx.x * PGD_THREADS + threadIdx.x; q < nq; q += stride) {
+    const float4 a1 = pgd_load<VEC>(x1, q, n), a2 = pgd_load<VEC>(x2, q, n);
+    float4 b1 = pgd_load<VEC>(g1, q, n), b2 = pgd_load<VEC>(g2, q, n);
+    const float4 c1 = pgd_load<VEC>(img1, q, n), c2 = pgd_load<VEC>(img2, q, n);
+    pgd_grad(b1.x, b2.x, joint);
+    pgd_grad(b1.y, b2.y, joint);
+    pgd_grad(b1.z, b2.z, joint);
+    pgd_grad(b1.w, b2.w, joint);
+    float4 y1, y2, e1, e2;
+    pgd_move(a1.x, b1.x, c1.x, a, y1.x, e1.x);
+    pgd_move(a2.x, b2.x, c2.x, a, y2.x, e2.x);
+    pgd_move(a1.y, b1.y, c1.y, a, y1.y, e1.y);
+    pgd_move(a2.y, b2.y, c2.y, a, y2.y, e2.y);
+    pgd_move(a1.z, b1.z, c1.z, a, y1.z, e1.z);
+    pgd_move(a2.z, b2.z, c2.z, a, y2.z, e2.z);
+    pgd_move(a1.w, b1.w, c1.w, a, y1.w, e1.w);
+    pgd_move(a2.w, b2.w, c2.w, a, y2.w, e2.w);
+    pgd_store<VEC>(x1, q, n, y1);
+    pgd_store<VEC>(x2, q, n, y2);
+    pgd_store<VEC>(d1, q, n, e1);
+    pgd_store<VEC>(d2, q, n, e2);
+    acc = pgd_sq(pgd_sq(pgd_sq(pgd_sq(acc, e1.x, e2.x), e1.y, e2.y), e1.z, e2.z), e1.w, e2.w);
+  }
+  const double sum = pgd_block_sum(acc, smem_e);
+  if (threadIdx.x == 0) ws[PGD_SCALARS + PGD_MAX_BLOCKS + blockIdx.x] = sum;
+}
+
+// x = clamp(img + s * e, 0, 1), product then sum (no fma); d = x - img from the updated x
+__device__ __forceinline__ void pgd_shrink(float img, float e, float s, float& x, float& d) {
+  x = fgsm_clamp01(pgd_add(img, pgd_mul(s, e)));
+  d = pgd_sub(x, img);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(PGD_THREADS) void pgd_l2_project_kernel(float* __restrict__ x1, float* __restrict__ x2,
+                                                                     const float* __restrict__ img1,
+                                                                     const float* __restrict__ img2, float* d1, float* d2,
+                                                                     double bound, long long n, double* __restrict__ ws) {
+  __shared__ double smem[4];
+  const double E = pgd_sum_partials(ws + PGD_SCALARS + PGD_MAX_BLOCKS, gridDim.x, smem);
+  float s = 1.f;
+  if (E < __builtin_inf()) {   // (false for NaN too: a non-finite E leaves the step as it is)
+    const double r = sqrt(E / (double)(2 * n));
+    if (r > bound) s = (float)(bound / r);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    ws[2] = E;
+    ws[3] = (double)s;
+  }
+  if (s == 1.f) return;   // inside the budget (or a quotient that rounds to 1): x = y and d = e stay, bit for bit
+  const long long nq = (n + 3) >> 2, stride = (long long)gridDim.x * PGD_THREADS;
+  for (long long q = (long long)blockIdx.x * PGD_THREADS + threadIdx.x; q < nq; q += stride) {
+    const float4 c1 = pgd_load<VEC>(img1, q, n), c2 = pgd_load<VEC>(img2, q, n);
+    const float4 e1 = pgd_load<VEC>(d1, q, n), e2 = pgd_load<VEC>(d2, q, n);
+    float4 y1, y2, f1, f2;
+    pgd_shrink(c1.x, e1.x, s, y1.x, f1.x);
+    pgd_shrink(c2.x, e2.x, s, y2.x, f2.x);
+    pgd_shrink(c1.y, e1.y, s, y1.y, f1.y);
+    pgd_shrink(c2.y, e2.y, s, y2.y, f2.y);
+    pgd_shrink(c1.z, e1.z, s, y1.z, f1.z);
+    pgd_shrink(c2.z, e2.z, s, y2.z, f2.z);
+    pgd_shrink(c1.w, e1.w, s, y1.w, f1.w);
+    pgd_shrink(c2.w, e2.w, s, y2.w, f2.w);
+    pgd_store<VEC>(x1, q, n, y1);
+    pgd_store<VEC>(x2, q, n, y2);
+    pgd_store<VEC>(d1, q, n, f1);
+    pgd_store<VEC>(d2, q, n, f2);
+  }
+}
+
+template <bool VEC>
+int pgd_l2_launch(float* x1, float* x2, const float* g1, const float* g2, const float* img1, const float* img2, float* d1,
+                  float* d2, float epsilon, float delta_bound, int joint, long long n, double* ws, hipStream_t s) {
+  long long blocks = ((n + 3) / 4 + PGD_THREADS - 1) / PGD_THREADS;
+  if (blocks > PGD_MAX_BLOCKS) blocks = PGD_MAX_BLOCKS;
+  const dim3 grid((unsigned)blocks), wg(PGD_THREADS);
+  pcfa_launch(pgd_l2_gsq_kernel<VEC>, grid, wg, 0, s, g1, g2, joint, n, ws + PGD_SCALARS);
+  PCFA_LAUNCH_CHECK();
+  pcfa_launch(pgd_l2_step_kernel<VEC>, grid, wg, 0, s, x1, x2, g1, g2, img1, img2, d1, d2, (double)epsilon, joint, n, ws);
+  PCFA_LAUNCH_CHECK();
+  pcfa_launch(pgd_l2_project_kernel<VEC>, grid, wg, 0, s, x1, x2, img1, img2, d1, d2, (double)delta_bound, n, ws);
+  PCFA_LAUNCH_CHECK();
+  return PCFA_OK;
+}
+
+}  // namespace
+
+extern "C" size_t pcfa_pgd_l2_workspace_bytes(void) { return sizeof(double) * (PGD_SCALARS + 2 * PGD_MAX_BLOCKS); }
+
+extern "C" int pcfa_pgd_l2_max_threads(void) { return PGD_MAX_BLOCKS * PGD_THREADS; }
+
+extern "C" int pcfa_pgd_l2_step(float* x1, float* x2, const float* g1, const float* g2, const float* img1, const float* img2,
+                                float* d1, float* d2, float epsilon, float delta_bound, int joint, long long n,
+                                void* workspace, void* stream) {
+  if (!x1 || !x2 || !g1 || !g2 || !img1 || !img2 || !d1 || !d2 || !workspace || n < 0 || (joint != 0 && joint != 1))
+    return PCFA_ERR_INVALID_ARG;
+  if (!(epsilon > 0.f && epsilon < __builtin_inff()) || !(delta_bound > 0.f && delta_bound < __builtin_inff()))
+    return PCFA_ERR_INVALID_ARG;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(x1) | reinterpret_cast<uintptr_t>(x2) | reinterpret_cast<uintptr_t>(g1) |
+                         reinterpret_cast<uintptr_t>(g2) | reinterpret_cast<uintptr_t>(img1) |
+                         reinterpret_cast<uintptr_t>(img2) | reinterpret_cast<uintptr_t>(d1) | reinterpret_cast<uintptr_t>(d2);
+  if ((bits & 3) || (reinterpret_cast<uintptr_t>(workspace) & 7)) return PCFA_ERR_INVALID_ARG;
+  if (n == 0) return PCFA_OK;
+  if ((bits & 15) == 0)   // ONE decision for all accesses of all three launches
+    return pgd_l2_launch<true>(x1, x2, g1, g2, img1, img2, d1, d2, epsilon, delta_bound, joint, n, (double*)workspace,
+                               (hipStream_t)stream);
+  return pgd_l2_launch<false>(x1, x2, g1, g2, img1, img2, d1, d2, epsilon, delta_bound, joint, n, (double*)workspace,
+                              (hipStream_t)stream);
+}

@@ -42,6 +42,12 @@ _FLAGS = [
     ("fgsm", "--epsilon", dict(default=0.00025, type=float, help="I-FGSM step size"), _FGSM),
     ("fgsm", "--pairs_in_flight", dict(default=1, type=int, help="NEW: independent pairs attacked side by side on every "
                                        "GPU (results identical to 1)"), _FGSM),
+    ("fgsm", "--step_norm", dict(default='sign', choices=['sign', 'l2'], help="NEW: the step of every iteration: 'sign' = "
+                                 "the signed gradient times --epsilon (I-FGSM), 'l2' = the gradient scaled to the averaged "
+                                 "L2 length --epsilon, then projected onto the averaged L2 ball of radius --delta_bound"),
+     _FGSM),
+    ("fgsm", "--delta_bound", dict(default=0.005, type=float, help="NEW for this attack: bound on the per-pixel averaged "
+                                   "L2 norm of the perturbation, the budget of --step_norm l2 (ignored by 'sign')"), _FGSM),
     ("pcfa", "--universal_perturbation", dict(action='store_true', default=False,
                                               help="one perturbation for the whole dataset"), _PCFA),
     ("pcfa", "--boxconstraint", dict(default='change_of_variables', choices=['clipping', 'change_of_variables'],

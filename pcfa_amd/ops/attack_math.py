@@ -162,6 +162,38 @@ def fgsm_step(x1, x2, g1, g2, image1, image2, d1, d2, epsilon, joint):
     _call("pcfa_fgsm_step", *[_ptr(t) for t in ts], float(epsilon), int(bool(joint)), n)
 
 
+_PGD_WS = {}   # (device index, lane) -> workspace of pgd_l2_step: the partials of two lanes never meet
+
+
+def pgd_l2_workspace(device):
+    """The lane's workspace of pgd_l2_step on `device` as float64 (allocated once, core.scratch_for): after a step
+    its first four entries are G, a, E, s (include/pcfa_hip.h).  Reading them waits for the GPU."""
+    device = torch.device(device)
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    key = (idx, current_lane())
+    ws = _PGD_WS.get(key)
+    if ws is None:
+        buf, _ = core.scratch_for("pcfa_pgd_l2_workspace_bytes", (), torch.device("cuda", idx))
+        ws = _PGD_WS[key] = buf.view(torch.float64)
+    return ws
+
+
+def pgd_l2_step(x1, x2, g1, g2, image1, image2, d1, d2, epsilon, delta_bound, joint):
+    """One projected-gradient iteration under the averaged-L2 budget, in place (attack_FGSM.pgd_l2_attack_step; the
+    arithmetic is stated in include/pcfa_hip.h): x_i moves by -a * gradient with a chosen so that the move has averaged
+    L2 length epsilon, is clamped to [0, 1] and, where two_norm_avg_delta(x1 - image1, x2 - image2) exceeds delta_bound,
+    pulled back towards the images by one factor s; d_i = x_i - image_i.  Three launches, no host read, capturable; the
+    scalars G, a, E, s stay in pgd_l2_workspace(device).  No autograd.  The same tensor checks as fgsm_step."""
+    ts = (x1, x2, g1, g2, image1, image2, d1, d2)
+    _dev(*ts)
+    n = x1.numel()
+    for t in ts:
+        if t.numel() != n or not t.is_contiguous():
+            raise ValueError("pgd_l2_step: eight dense tensors of one size, got %s" % [tuple(t_.shape) for t_ in ts])
+    _call("pcfa_pgd_l2_step", *[_ptr(t) for t in ts], float(epsilon), float(delta_bound), int(bool(joint)), n,
+          _ptr(pgd_l2_workspace(x1.device)))
+
+
 _WS = {}
 
 

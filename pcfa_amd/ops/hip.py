@@ -22,6 +22,7 @@ Operator boundaries mirrored (reference file:line) -- one module per group:
   attack_math  box_transform, extract_deltas(_joint), loss_delta_constraint, avg_epe, two_norm_*, pm1_pair
                                                               helper_functions/own_models.py:62-85, attack_PCFA.py:20-37, losses.py
                fgsm_step                                      attack_FGSM.py:21-56,208-209
+               pgd_l2_step, pgd_l2_workspace                  (no counterpart: `--step_norm l2`, attack_FGSM.pgd_l2_attack_step)
   digest       tensor_digest                                  (no counterpart: the record of pcfa_amd.trace.ClosureTrace)
 """
 from .. import _hip  # noqa: F401

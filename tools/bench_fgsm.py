@@ -13,6 +13,11 @@ iterations/s = pairs x steps / wall time.  Legs:
     graph     captured forward / backward; the graph set is captured by an untimed first pair and adopted by every rep,
               as by every later pair of a dataset
     lanes N   N pairs in flight (attack_PCFA.PairsInFlight), graph sets adopted likewise
+    l2        `graph` with `--step_norm l2` (ops.pgd_l2_step: three launches between the replays instead of one) under
+              `--delta_bound`; a graph set of its own, adopted likewise.  Another attack, so `same_result_as_graph` is
+              null for it; its line carries the final `l2_delta-avg` next to the bound instead
+
+`--legs` restricts the run to some of them (the order of the table above is kept).
 
 Prints one JSON line per (network, leg): median, min and max of iterations/s over the reps, and every rep's figure.
 
@@ -54,6 +59,8 @@ def main(argv=None):
     ap.add_argument("--joint", action="store_true")
     ap.add_argument("--weights", default="random:1234")
     ap.add_argument("--parent", default=None, help="attack_FGSM.py of the checkout to compare with")
+    ap.add_argument("--delta_bound", type=float, default=0.005, help="the budget of the l2 leg")
+    ap.add_argument("--legs", nargs="+", default=None, help="run only these legs (parent, eager, graph, lanes, l2)")
     opt = ap.parse_args(argv)
     if max(opt.lanes, default=1) >= 4:
         os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")     # before the runtime starts (attack_PCFA._hardware_queues_for)
@@ -76,7 +83,9 @@ def main(argv=None):
                          save_frequency=1, output_folder="experiment_data", pairs_in_flight=1)
         model = attack_PCFA._load_model(args, dev, variable_change=False)
 
-        def solo(use_graph):
+        args_l2 = Namespace(**dict(vars(args), step_norm="l2", delta_bound=opt.delta_bound))
+
+        def solo(use_graph, args=args):
             st = attack_FGSM.FgsmAttack(model, *pairs[0], 0, dev, True, args, use_graph=use_graph)
             for _ in range(opt.steps):
                 st.step()
@@ -93,6 +102,9 @@ def main(argv=None):
             legs.append(("parent", lambda: (1, parent.fgsm_attack(model, *pairs[0], dev, True, args))))
         legs += [("eager", lambda: solo(False)), ("graph", lambda: solo(True))]
         legs += [("lanes %d" % n, (lambda n=n: flight(n))) for n in opt.lanes if n > 1]
+        legs.append(("l2", lambda: solo(True, args_l2)))
+        if opt.legs is not None:
+            legs = [(name, fn) for name, fn in legs if name.split()[0] in opt.legs]
         results = {}
         for name, fn in legs:                      # untimed: first-call work, weight packs, graph capture
             _, results[name] = fn()
@@ -105,15 +117,16 @@ def main(argv=None):
                 n, _ = fn()
                 torch.cuda.synchronize()
                 rates[name].append(n * opt.steps / (time.perf_counter() - t0))
-        final = results["graph"]
+        final = results.get("graph")
         for name, _ in legs:
             r = rates[name]
             res = results[name][0] if isinstance(results[name], list) else results[name]   # pair 0 in every leg
-            same = all(res[k] == final[k] for k in final if k != "history")
+            same = None if (final is None or name == "l2") else all(res[k] == final[k] for k in final if k != "history")
+            extra = {"l2_delta_avg": res["l2_delta-avg"], "delta_bound": opt.delta_bound} if name == "l2" else {}
             print(json.dumps({"net": net, "size": opt.size, "steps": opt.steps, "loss": opt.loss, "joint": opt.joint,
                               "leg": name, "iters_per_s_median": round(statistics.median(r), 3),
                               "iters_per_s_min": round(min(r), 3), "iters_per_s_max": round(max(r), 3),
-                              "reps": [round(v, 3) for v in r], "same_result_as_graph": same}), flush=True)
+                              "reps": [round(v, 3) for v in r], "same_result_as_graph": same, **extra}), flush=True)
         del model
         torch.cuda.empty_cache()
 
