@@ -19,7 +19,8 @@
 // tile:   idx(l, y, x) = off[l] + ((y>>2)*tw[l] + (x>>2))*16 + (y&3)*4 + (x&3).
 // A (2r+2)^2 lookup window then touches ~11 sectors instead of ~16-20 with plain rows, and a
 // wave fetches a whole window with ONE 16-B-per-lane load (lane = tile row).  Levels are padded
-// to whole tiles; pad texels hold 0 (the GEMM multiplies zero columns of f2ext).
+// to whole tiles; pad texels and the closing zero tile hold +0 in every slab the forward builds: the GEMM multiplies zero
+// columns of f2ext there, and the pooled epilogue (gemm_tile.hpp) stores zeros into the pad rows of levels 1 and 2.
 struct PyrLayout {
   int L;
   int h[PCFA_MAX_LEVELS];

@@ -325,9 +325,9 @@ def test_pyramid_forward_vs_float64(record_property, shape):
     element bound with n6 + 3 l and the statistical gate with the fp32 pyramid test's n = D + 3 l + 2: three additions
     per 2x2 average, of the accumulators in the epilogue or of fmap2 in f2ext; the scale 1/16 is exact.  Every texel of
     every level is written.  Tile-padding columns and the closing zero tile are exactly 0 -- except, on the pooled
-    epilogue, the pad texels of levels 1 and 2: the shared epilogue (gemm_tile.hpp) writes those two levels from the
-    level-0 tiles it holds, which reach every texel of the levels but not every pad row when H % 16 != 0; the fp32
-    twin leaves the same texels unwritten and no lookup reads them.  Two calls give equal bits."""
+    epilogue, the pad texels of levels 1 and 2, which this test leaves unexamined when H % 16 != 0 (the shared
+    epilogue, gemm_tile.hpp, once left some of those pad rows unwritten; it zeroes them now, and
+    tests/test_pyramid_f64_gpu.py asserts +0 in every float outside the level texels).  Two calls give equal bits."""
     B, H, W = shape
     D, L = 256, 4
     lib = _hip.load()
