@@ -35,7 +35,7 @@ extern "C" {
 #endif
 
 #define PCFA_MAX_LEVELS 8
-#define PCFA_ABI_VERSION 2
+#define PCFA_ABI_VERSION 3
 
 /* f_type of the similarity term: helper_functions/losses.py:145-174 */
 #define PCFA_LOSS_AEE 0
@@ -932,6 +932,38 @@ PCFA_API int pcfa_avg_epe_items(const float* flow1, const long long strides1[4],
                                 const long long strides2[4], int items, int H, int W, float* out, void* workspace,
                                 void* stream);
 PCFA_API int pcfa_sum_squares_items(const float* x, int items, long long n, float* out, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * Picture artefacts (`--save_png`): packed 8-bit RGB straight from the device
+ * (helper_functions/logging.py:289-339, ownutilities.py:363-505,
+ * flow_library/flow_plot.py:56-105).  Inputs are [items][C][H][W] fp32 views
+ * with four element strides (b, c, h, w), as pcfa_avg_epe takes them; pictures
+ * are dense uint8 [items][H][W][3].  Every scale is read from device memory, so
+ * no host read sits between the launches of a pair's pictures.  Arguments are
+ * validated before any launch: null pointers and non-positive sizes are
+ * PCFA_ERR_INVALID_ARG.  (These entry points came with PCFA_ABI_VERSION 3.)
+ * ------------------------------------------------------------------------- */
+/* out[b] = max over item b's pixels of sqrt(u^2 + v^2), each operation rounded once (numpy's fp32 result); a pixel with
+ * a NaN component counts as 0.  A maximum does not depend on the order of reduction: two calls give equal bits. */
+PCFA_API int pcfa_flow_maxlen_items(const float* flow, const long long strides[4], int items, int H, int W, float* out,
+                                    void* stream);
+/* out[b] = max |x| over the n floats at x + b*n (NaN elements are skipped). */
+PCFA_API int pcfa_absmax_items(const float* x, int items, long long n, float* out, void* stream);
+/* colorplot_light per pixel with item b's scale[b]: u, v /= scale[b] + 1e-5; rad = |(u, v)|; the angle
+ * atan2(-v, -u) picks two neighbours of the 55-entry Middlebury wheel, blended linearly; rad <= 1: col = 1 - rad (1 - col),
+ * else col *= 0.75; out = floor(255 col).  NaN pixels are (0, 0, 0); scale 0 gives a white picture.  With scale[b] the
+ * item's own maximum m, the longest vector has rad = m / (m + 1e-5): for m above about 20 that is within fp32 rounding of
+ * the rad = 1 step and its pixels may take the darkened branch (as in the reference's fp32 arithmetic). */
+PCFA_API int pcfa_flow_colour_u8(const float* flow, const long long strides[4], const float* scale, int items, int H,
+                                 int W, unsigned char* out, void* stream);
+/* v = x (+ add, NULL or a second view with strides of its own; a zero item stride shares one perturbation among the
+ * items); with m (NULL or device scalars, item b reads m[b * m_stride]) v = v / m / 2 + 0.5; out = v * 255 (v itself
+ * when unit_input == 0 and m is NULL: input in levels already) truncated toward zero and SATURATED: NaN and negatives
+ * give 0, values above 255 give 255.  C = 3.  One rounding per operation, no contraction: the plain and the add path
+ * give the bits of fp32 x * 255 and (x + add) * 255. */
+PCFA_API int pcfa_image_u8(const float* x, const long long strides[4], const float* add, const long long add_strides[4],
+                           const float* m, long long m_stride, int unit_input, int items, int H, int W,
+                           unsigned char* out, void* stream);
 
 /* ------------------------------------------------------------------------- *
  * L-BFGS vector math of the attack loop: the memory update and the two-loop

@@ -8,7 +8,7 @@ import ctypes
 import os
 from ctypes import c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_uint, c_ulonglong, c_void_p, POINTER
 
-ABI_VERSION = 2
+ABI_VERSION = 3
 LIB_PATH = os.environ.get("PCFA_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib",
                                                           "libpcfa_hip.so")  # PCFA_HIP_LIB: A/B builds of the same ABI
 
@@ -218,6 +218,11 @@ SIGNATURES = {
     "pcfa_lbfgs_gram_update_items": (c_int, [_P, _P, _P, POINTER(c_float), _P, _P, _P, _P, c_int, c_longlong, c_int,
                                              c_uint, _P]),
     "pcfa_lbfgs_gram_direction_items": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_longlong, c_int, c_uint, _P]),
+    # picture artefacts (--save_png): fp32 views in, dense uint8 [items,H,W,3] out, scales read from device memory
+    "pcfa_flow_maxlen_items": (c_int, [_P, _S4, c_int, c_int, c_int, _P, _P]),
+    "pcfa_absmax_items": (c_int, [_P, c_int, c_longlong, _P, _P]),
+    "pcfa_flow_colour_u8": (c_int, [_P, _S4, _P, c_int, c_int, c_int, _P, _P]),
+    "pcfa_image_u8": (c_int, [_P, _S4, _P, _S4, _P, c_longlong, c_int, c_int, c_int, c_int, _P, _P]),
 }
 
 MAX_ITEMS = 16   # PCFA_MAX_ITEMS

@@ -24,7 +24,7 @@ import torch
 
 from . import config, graph_sets, ops, sharding
 from .attack_PCFA import PairsInFlight, _graphs_enabled, _hardware_queues_for, _load_model, _should_save, select_device
-from .helper_functions import datasets, logging, losses, ownutilities, parsing_file, targets
+from .helper_functions import datasets, logging, losses, ownutilities, parsing_file, pictures, targets
 
 # columns of the per-iteration history, under the reference's metric names (attack_FGSM.py:234-241)
 HISTORY_KEYS = ("aee_predadv-tgt", "aee_pred-predadv", "aee_predadv-gt", "l2_delta1", "l2_delta2", "l2_delta-avg")
@@ -360,6 +360,24 @@ class FgsmAttack:
             logging.save_tensor(tens, name, batch, distortion_folder)
         if self.flow_gt is not None:
             logging.save_tensor(self.flow_gt, "flow_gt", batch, distortion_folder)
+        if getattr(self.args, "save_png", False):
+            self._save_pictures(distortion_folder)
+
+    def _save_pictures(self, distortion_folder):
+        """`--save_png`: the pictures of attack_FGSM.py:256-278, queued on the current stream like PairAttack's.  The
+        perturbations are normalised to their common max |delta| as in attack_PCFA.py (the reference's FGSM script takes
+        max(delta) without the absolute value, which is not positive for a perturbation that only darkens)."""
+        joint = bool(self.args.joint_perturbation)
+        ps = pictures.PictureSet()
+        logging.save_attack_pictures(
+            ps, [self.batch], distortion_folder,
+            images=(("image1", self.image1, None), ("image2", self.image2, None)),
+            deltas=(("delta1", self.delta1), (None if joint else "delta2", self.delta2)),
+            flows=(("flow_pred_final", self.flow_pred), ("flow_pred_init", self.flow_pred_init),
+                   ("flow_target", self.target), ("flow_gt", self.flow_gt)),
+            flow_scale=logging.flow_picture_scale(getattr(self.args, "png_flow_scale", "own"),
+                                                  (self.flow_gt, self.flow_pred_init, self.flow_pred)))
+        ps.write()
 
 
 def fgsm_attack(model, image1, image2, flow, device, has_gt, args, batch=0, distortion_folder=None):
@@ -415,8 +433,9 @@ def attack(args, data_loader=None, has_gt=None):
                                                     args), len(group), device)
         if args.steps > 0:
             flight.run(args.steps)
-        for st in flight.attacks:
-            r = _finish_pair(st, distortion_folder)
+        for k, st in enumerate(flight.attacks):
+            with flight.on_lane(k):     # save() queues its conversions and copies on the lane's own stream
+                r = _finish_pair(st, distortion_folder)
             rows.append((st.batch,) + tuple(r[k] for k in keys))
 
     for batch, (image1, image2, flow, _) in enumerate(data_loader):

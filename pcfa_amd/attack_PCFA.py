@@ -20,6 +20,7 @@ round-robin over ranks with no collective in the data path (`attack_l2`); the un
 is data parallel over the batch with ONE all-reduce of d(loss)/d(delta) per closure
 (`attack_l2_universal`), see pcfa_amd/sharding.py.
 """
+import contextlib
 import os
 import time
 
@@ -28,7 +29,7 @@ import torch
 
 from . import _hip, config, graph_sets, ops, sharding
 from .graph_sets import _log_eviction
-from .helper_functions import datasets, logging, losses, ownutilities, parsing_file, targets
+from .helper_functions import datasets, logging, losses, ownutilities, parsing_file, pictures, targets
 from .helper_functions.config_paths import Conf
 
 EPS_BOX = 1e-7  # attack_PCFA.py:608
@@ -252,6 +253,7 @@ class _AttackState:
         self.delta1, self.delta2 = torch.zeros_like(self.image1), torch.zeros_like(self.image2)
         self.steps_done = 0
         self.closures = 0          # evaluations of the closure (each one is a closure evaluation of every item)
+        self._pictured = set()     # items whose pictures --save_png has written
         if use_graph and kept is None:
             self.enable_graph()
 
@@ -350,6 +352,46 @@ class _AttackState:
             logging.save_tensor(tens, name, r.batch, distortion_folder)
         if self.has_gt:
             logging.save_tensor(self._item(self.flow_gt, b), "flow_gt", r.batch, distortion_folder)
+        if getattr(self.args, "save_png", False):
+            self._save_pictures(distortion_folder, b)
+
+    def _save_pictures(self, distortion_folder, b):
+        """`--save_png`: the pictures of attack_PCFA.py:267-292, for ALL pairs of this state at the first pair saved: every
+        conversion is one launch over the items.  Launches and device-to-host copies are queued on the current stream
+        inside save() -- the stream the pair ran on; under --pairs_in_flight the driver makes the lane's stream current
+        (PairsInFlight.on_lane) -- so stream order keeps them ahead of the uploads of the next pair(s) that adopt the static
+        buffers."""
+        if b in self._pictured:
+            return
+        items = [i for i in range(len(self.rec)) if _should_save(self.rec[i].batch, self.args)]
+        self._pictured.update(items)
+        everyone = len(items) == len(self.rec)
+
+        def pick(t):   # the rows of the pairs that are saved
+            if t is None:
+                return None
+            return t.detach() if everyone else torch.cat([self._item(t, i).detach() for i in items])
+
+        def best(name, last):   # the best iterate; a pair that never took a step has only its last (= initial) state
+            return torch.cat([self._item(last, i).detach() if getattr(self.rec[i], name) is None
+                              else getattr(self.rec[i], name) for i in items])
+
+        d1, d2 = best("delta1_min", self.delta1), best("delta2_min", self.delta2)
+        flow_best = best("flow_pred_min", self.flow_pred)
+        image1, image2 = pick(self.image1), pick(self.image2)
+        flow_init, flow_gt = pick(self.flow_pred_init), pick(self.flow_gt) if self.has_gt else None
+        joint = bool(self.args.joint_perturbation)
+        ps = pictures.PictureSet()
+        logging.save_attack_pictures(
+            ps, [self.rec[i].batch for i in items], distortion_folder,
+            images=(("image1", image1, None), ("image2", image2, None), ("image1_delta_best", image1, d1),
+                    ("image2_delta_best", image2, d2)),
+            deltas=(("delta1_best", d1), (None if joint else "delta2_best", d2)),
+            flows=(("flow_pred_best", flow_best), ("flow_pred_init", flow_init), ("flow_target", pick(self.target)),
+                   ("flow_gt", flow_gt)),
+            flow_scale=logging.flow_picture_scale(getattr(self.args, "png_flow_scale", "own"),
+                                                  (flow_gt, flow_init, flow_best)))
+        ps.write()
 
     def result(self, b=0):
         """Pair b's 12-tuple (attack_PCFA.py:294)."""
@@ -639,6 +681,14 @@ class PairsInFlight:
                              "products would share one handle's workspace): build the model with gma_gemm='hip' "
                              "(PCFA_GMA_GEMM=hip) or use --pairs_in_flight 1")
 
+    @contextlib.contextmanager
+    def on_lane(self, k):
+        """The caller's thread as lane k: its scratch keys and its stream current.  What touches a lane's static buffers
+        after run() -- save() with its picture conversions and copies -- is queued here, so that stream order keeps it ahead
+        of the uploads of the next pair that adopts those buffers on the same stream."""
+        with ops.core.lane(k), torch.cuda.stream(self.streams[k]):
+            yield self.attacks[k]
+
     def run(self, steps):
         """`steps` attack steps on every lane, concurrently; returns each lane's last (aee_adv_tgt, aee_adv_pred, l2)."""
         import threading
@@ -732,10 +782,11 @@ def attack_l2(args, data_loader=None, has_gt=None):
                                len(group), device)
         if args.steps > 0:
             flight.run(args.steps)
-        for (batch, _, _, _), st in zip(group, flight.attacks):
+        for k, ((batch, _, _, _), st) in enumerate(zip(group, flight.attacks)):
             _save_trace(st, args)
             if distortion_folder is not None and _should_save(batch, args):
-                st.save(distortion_folder)
+                with flight.on_lane(k):     # on the lane's own stream: the next group adopts its buffers there
+                    st.save(distortion_folder)
             local.append(_result_row(batch, st.result()))
 
     def attack_batch(group):
@@ -753,17 +804,20 @@ def attack_l2(args, data_loader=None, has_gt=None):
 
     mine = ((batch, image1, image2, flow) for batch, (image1, image2, flow, _) in enumerate(data_loader)
             if batch % world == rank)
-    if per_closure > 1:
-        for group in group_pairs(mine, per_closure, lambda pair: tuple(pair[1].shape)):
-            attack_batch(group)
-    else:
-        for pair in mine:
-            pending.append(pair)
-            if len(pending) == nflight:
+    # --save_png: a pair's pictures are deflated and written by one worker thread while the next pair is attacked; leaving
+    # the block joins it and re-raises its error
+    with pictures.background_writes() if getattr(args, "save_png", False) else contextlib.nullcontext():
+        if per_closure > 1:
+            for group in group_pairs(mine, per_closure, lambda pair: tuple(pair[1].shape)):
+                attack_batch(group)
+        else:
+            for pair in mine:
+                pending.append(pair)
+                if len(pending) == nflight:
+                    attack_group(pending)
+                    pending = []
+            if pending:
                 attack_group(pending)
-                pending = []
-        if pending:
-            attack_group(pending)
 
     rows = sharding.gather_rows(local, width=13, device=device)
     if rank != 0:
@@ -836,6 +890,7 @@ class UniversalAttack:
         self.states = {}   # batch shape -> _UniversalBatchState
         self.st = None
         self.flow_pred_init = None
+        self.flow_pred = None      # the attacked prediction of the last step (--save_png)
         self.closures = 0
 
     def deltas(self):
@@ -895,6 +950,7 @@ class UniversalAttack:
         self.st = st
         with torch.no_grad():
             self.flow_pred_init = self.predict(perturbed=False).detach().clone()
+        self.flow_pred = None
         target = targets.get_target(self.args.target, self.flow_pred_init,
                                     custom_target_path=self.args.custom_target_path, device=device).to(device)
         if st.target is None:
@@ -925,6 +981,7 @@ class UniversalAttack:
         else:
             with torch.no_grad():
                 flow_pred = self.predict()
+        self.flow_pred = flow_pred
         d1, d2 = self.deltas()
         aee_adv_tgt, aee_adv_pred = logging.calc_metrics_adv(flow_pred, st.target, self.flow_pred_init)
         if self.world > 1:
@@ -932,6 +989,27 @@ class UniversalAttack:
         l2_delta1, l2_delta2, l2_delta12 = logging.calc_delta_metrics(d1.detach(), d2.detach())
         return {"aee_predadv-tgt": aee_adv_tgt, "aee_pred-predadv": aee_adv_pred, "l2_delta1": l2_delta1,
                 "l2_delta2": l2_delta2, "l2_delta-avg": l2_delta12}
+
+    def save_pictures(self, distortion_folder, batch_ctr, epoch, flow_gt=None):
+        """`--save_png`: the per-epoch pictures of attack_PCFA.py:526-541 from the last batch's tensors: the perturbations
+        normalised to their common maximum, the attacked frames and the attacked prediction (item i of the batch under the
+        reference's rule: `<name>.png`, then `<name>.png_i.png`)."""
+        st, e = self.st, str(epoch)
+        d1, d2 = (d.detach().unsqueeze(0) for d in self.deltas())
+        joint = bool(self.args.joint_perturbation)
+        flow_pred = self.flow_pred if self.flow_pred is not None else self.flow_pred_init
+        ps = pictures.PictureSet()
+        m = torch.maximum(ops.get().absmax(d1), ops.get().absmax(d2))
+        logging.save_image(d1, batch_ctr, distortion_folder, image_name="delta1_e" + e, normalize_max=m, pictures=ps)
+        if not joint:
+            logging.save_image(d2, batch_ctr, distortion_folder, image_name="delta2_e" + e, normalize_max=m, pictures=ps)
+        logging.save_image(st.image1, batch_ctr, distortion_folder, image_name="image1_delta_e" + e, add=d1, pictures=ps)
+        logging.save_image(st.image2, batch_ctr, distortion_folder, image_name="image2_delta_e" + e, add=d2, pictures=ps)
+        scale = logging.flow_picture_scale(getattr(self.args, "png_flow_scale", "own"),
+                                           (flow_gt, self.flow_pred_init, flow_pred))
+        logging.save_flow(flow_pred, batch_ctr, distortion_folder, flow_name="flow_pred_e" + e, auto_scale=False,
+                          max_scale=scale, honour_scale=scale is not None, pictures=ps)
+        ps.write()
 
     @property
     def graphed(self):
@@ -981,6 +1059,8 @@ def attack_l2_universal(args, data_loader=None, has_gt=None):
             logging.save_tensor(ua.nw_delta1, "delta1_e" + str(epoch), batch_ctr, distortion_folder)
             if not args.joint_perturbation:
                 logging.save_tensor(ua.nw_delta2, "delta2_e" + str(epoch), batch_ctr, distortion_folder)
+            if getattr(args, "save_png", False):
+                ua.save_pictures(distortion_folder, batch_ctr, epoch, flow.to(device) if has_gt else None)
     return {"delta1": ua.nw_delta1.detach(), "delta2": ua.deltas()[1].detach(), "history": history,
             "batches": batches, "collectives": ua.reducer.collectives if ua.reducer is not None else 0,
             "batch_sum_collectives": ua.batch_sums.collectives if ua.batch_sums is not None else 0,

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import losses, ownutilities
+from . import pictures as _pictures
 
 
 class MetricSink:
@@ -101,3 +102,81 @@ def save_tensor(tens, tensor_name, batch, output_folder, unregistered_artifacts=
     path = os.path.join(output_folder, "%05d_%s.npy" % (batch, tensor_name))
     np.save(path, tens.detach().cpu().numpy().astype(np.float32))
     return path
+
+
+def _picture_path(batch, name, output_folder):
+    return os.path.join(output_folder, "%05d_%s.png" % (batch, name))
+
+
+def save_image(image_data, batch, output_folder, image_name='image', unit_input=True, normalize_max=None,
+               unregistered_artifacts=True, add=None, pictures=None):
+    """`{batch:05d}_{name}.png` (logging.py:289-317): the image times 255 (unit_input), or with normalize_max = m
+    (a number or a device tensor) image / m / 2 + 0.5, times 255 -- the perturbation picture.  Converted on the GPU
+    (ops.image_to_rgb8: out-of-range values saturate).  Extra keywords of this build: `add`, a perturbation added in the
+    same launch (the reference's save_image(image + delta, ...)); `pictures`, a pictures.PictureSet that collects the
+    picture for one common write()."""
+    if image_data is None or output_folder is None:
+        return None
+    path = _picture_path(batch, image_name, output_folder)
+    ps = _pictures.PictureSet() if pictures is None else pictures
+    t = image_data.detach()
+    items = t.shape[0] if t.dim() == 4 else 1
+    if normalize_max is not None:
+        normalize_max = _pictures.on_device(normalize_max, t.device)
+    ps.add_image(_pictures.item_paths(path, items), t, add=add, normalize_max=normalize_max, unit_input=unit_input)
+    if pictures is None:
+        ps.write()
+    return path
+
+
+def save_flow(flow, batch, output_folder, flow_name='flowgt', auto_scale=True, max_scale=-1, unregistered_artifacts=True,
+              honour_scale=False, pictures=None):
+    """`{batch:05d}_{name}.png` in the Middlebury colour code (logging.py:320-339).  As in the reference the picture is
+    scaled to its own longest vector WHATEVER auto_scale / max_scale say (ownutilities.quickvisualization_flow drops
+    them there); honour_scale=True passes them on."""
+    if flow is None or output_folder is None:
+        return None
+    path = _picture_path(batch, flow_name, output_folder)
+    ownutilities.quickvisualization_flow(flow.detach(), path, auto_scale=auto_scale, max_scale=max_scale,
+                                         honour_scale=honour_scale, pictures=pictures)
+    return path
+
+
+def flow_picture_scale(mode, flows):
+    """The scale of a pair's flow pictures under `--png_flow_scale`: None for 'own' (every picture to its own longest
+    vector, what the reference writes), for 'shared' the per-item maximum over `flows` (ground truth if any, initial and
+    attacked prediction) of ops.flow_maxlen -- a device tensor; nothing is read back (what attack_PCFA.py:281-292 means
+    to do)."""
+    if mode != "shared":
+        return None
+    from .. import ops
+    scale = None
+    for f in flows:
+        if f is not None:
+            m = ops.get().flow_maxlen(f)
+            scale = m if scale is None else torch.maximum(scale, m)
+    return scale
+
+
+def save_attack_pictures(pictures, batches, output_folder, images=(), deltas=(), flows=(), flow_scale=None):
+    """Queue one attack's pictures on `pictures` for the pairs numbered `batches` (one per item of the tensors).
+    images: (name, tensor, add or None); deltas: (name, tensor) normalised to their common per-item maximum (the
+    reference's max_delta); flows: (name, tensor), scaled by flow_scale (flow_picture_scale; None: own maximum)."""
+    from .. import ops
+
+    def paths(name):
+        return [_picture_path(b, name, output_folder) for b in batches]
+
+    for name, tens, add in images:
+        pictures.add_image(paths(name), tens, add=add)
+    if deltas:
+        max_delta = None
+        for _, d in deltas:
+            m = ops.get().absmax(d.detach().reshape(len(batches), -1))
+            max_delta = m if max_delta is None else torch.maximum(max_delta, m)
+        for name, d in deltas:
+            if name is not None:
+                pictures.add_image(paths(name), d, normalize_max=max_delta)
+    for name, f in flows:
+        if f is not None:
+            pictures.add_flow(paths(name), f, ops.get().flow_maxlen(f) if flow_scale is None else flow_scale)

@@ -3,11 +3,18 @@
 Mirror of the model half of the reference's helper_functions/ownutilities.py:
     InputPadder :21-62   import_and_load :64-169   preprocess_img :241-280
     postprocess_flow :283-299   compute_flow :302-343   model_takes_unit_input :347-360
+and of its picture helpers:
+    flow_length :363-376   maximum_flow :379-389   quickvis_tensor / quickvisualization_tensor :392-441
+    quickvis_flow / quickvisualization_flow :444-505
 Same names, argument meaning and error behaviour.  Deliberate differences:
   * postprocess_flow keeps the flow on its device (the reference's `.cpu()`, :297, forces a
     device sync + PCIe round trip on every forward);
   * RAFT / GMA are not wrapped in torch.nn.DataParallel (one process per GPU); the "module."
     prefix of the public checkpoints is stripped on load;
+  * the picture helpers convert on the GPU (ops.artefacts) and write PNG through helper_functions/png.py -- no Pillow;
+    out-of-range image values saturate instead of wrapping (ops.image_to_rgb8);
+  * flow_length returns the true length sqrt(u^2 + v^2); the reference's returns sqrt(u + v) (:373-376 squares the flow
+    and then sums the unsquared one).  maximum_flow below has always computed the true maximum and is unchanged;
   * `weights=` keyword: "pretrained" (default, the reference's files under Paths.config("weights"))
     or "random:<seed>" for the synthetic benchmark / tests where no checkpoints exist.
 """
@@ -18,6 +25,8 @@ from argparse import Namespace
 import torch
 import torch.nn.functional as F
 
+from .. import ops
+from . import pictures as pic
 from .config_paths import Paths
 
 RAFT_CONFIG = {"epsilon": 1e-8, "small": False, "mixed_precision": False, "alternate_correlation": False}
@@ -202,3 +211,71 @@ def maximum_flow(flow):
     else:
         mag = torch.sqrt(torch.sum(f * f, dim=0))
     return torchfloat_to_float64(torch.max(mag))
+
+
+def flow_length(flow):
+    """Length sqrt(u^2 + v^2) of every vector of a (b,2,H,W) or (2,H,W) field, as (b,1,H,W) or (1,H,W) (the documented
+    contract of ownutilities.py:363-376, whose code returns sqrt(u + v) instead)."""
+    return torch.sqrt(torch.sum(torch.pow(flow, 2), -3, keepdim=True))
+
+
+def quickvis_tensor(t, filename, pictures=None):
+    """Save a (3,H,W) or (1,3,H,W) tensor of levels 0..255 as a PNG (ownutilities.py:392-417).  `pictures`: a
+    pictures.PictureSet that collects the picture instead (its write() then writes it)."""
+    if not (t.dim() == 3 or (t.dim() == 4 and t.size()[0] == 1)):
+        print("Encountered invalid tensor dimensions %s, abort printing." % str(t.size()))
+        return
+    ps = pic.PictureSet() if pictures is None else pictures
+    ps.add_image([filename], t, unit_input=False)
+    if pictures is None:
+        ps.write()
+
+
+def quickvisualization_tensor(t, filename, pictures=None):
+    """Save a batch (>= 1) of image tensors of levels 0..255 (ownutilities.py:421-441): item 0 goes to `filename`, item i
+    to `filename + "_i.png"`; all items are converted by one launch."""
+    if t.dim() == 3 or (t.dim() == 4 and t.size()[0] == 1):
+        return quickvis_tensor(t, filename, pictures)
+    if t.dim() != 4:
+        print("Encountered unprocessable tensor dimensions %s, abort printing." % str(t.size()))
+        return
+    ps = pic.PictureSet() if pictures is None else pictures
+    ps.add_image(pic.item_paths(filename, t.size()[0]), t, unit_input=False)
+    if pictures is None:
+        ps.write()
+
+
+def _flow_scale(flow, auto_scale, max_scale):
+    return ops.get().flow_maxlen(flow) if auto_scale else pic.on_device(max_scale, flow.device)
+
+
+def quickvis_flow(flow, filename, auto_scale=True, max_scale=-1, pictures=None):
+    """Save a (2,H,W) or (1,2,H,W) flow field in the Middlebury colour code (ownutilities.py:444-478): scaled to its own
+    longest vector, or with auto_scale=False to `max_scale` (a number or a device tensor)."""
+    if not (flow.dim() == 3 or (flow.dim() == 4 and flow.size()[0] == 1)):
+        print("Encountered invalid tensor dimensions %s, abort printing." % str(flow.size()))
+        return
+    ps = pic.PictureSet() if pictures is None else pictures
+    ps.add_flow([filename], flow, _flow_scale(flow, auto_scale, max_scale))
+    if pictures is None:
+        ps.write()
+
+
+def quickvisualization_flow(flow, filename, auto_scale=True, max_scale=-1, honour_scale=False, pictures=None):
+    """Save a batch (>= 1) of flow fields (ownutilities.py:481-505), item i under the batch rule of
+    quickvisualization_tensor, one launch for all items.
+
+    The reference's function drops `auto_scale` and `max_scale` and scales every picture to its own longest vector; so
+    does this one unless honour_scale=True (`--png_flow_scale shared`), which passes them on as quickvis_flow takes them
+    (max_scale: a number, or a device tensor of one value or of one per item)."""
+    if not honour_scale:
+        auto_scale, max_scale = True, -1
+    if flow.dim() == 3 or (flow.dim() == 4 and flow.size()[0] == 1):
+        return quickvis_flow(flow, filename, auto_scale=auto_scale, max_scale=max_scale, pictures=pictures)
+    if flow.dim() != 4:
+        print("Encountered unprocessable tensor dimensions %s, abort printing." % str(flow.size()))
+        return
+    ps = pic.PictureSet() if pictures is None else pictures
+    ps.add_flow(pic.item_paths(filename, flow.size()[0]), flow, _flow_scale(flow, auto_scale, max_scale))
+    if pictures is None:
+        ps.write()

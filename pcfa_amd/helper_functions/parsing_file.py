@@ -33,6 +33,17 @@ _FLAGS = [
     ("saving", "--small_save", dict(action='store_true', help="artefacts for the first 32 pairs only"), _ALWAYS),
     ("saving", "--save_frequency", dict(type=int, default=1, help="save artefacts every N-th pair"), _ALWAYS),
     ("saving", "--no_save", dict(action='store_true', help="write no artefacts at all"), _ALWAYS),
+    ("saving", "--save_png", dict(action='store_true', default=False,
+                                  help="NEW here: with every saved pair also write the reference's pictures as "
+                                  "NNNNN_<name>.png: the frames, the attacked frames, the perturbations normalised to "
+                                  "their common maximum and the flow fields in the Middlebury colour code (converted on "
+                                  "the GPU)"), _ALWAYS),
+    ("saving", "--png_flow_scale", dict(default='own', choices=['own', 'shared'],
+                                        help="NEW: scale of the flow pictures of --save_png. 'own' = every picture to its "
+                                        "own longest vector, which is what the reference writes (its "
+                                        "quickvisualization_flow drops the scale it is given); 'shared' = one scale for a "
+                                        "pair's pictures, the longest vector of ground truth (if any), initial and "
+                                        "attacked prediction, which is what the reference intended"), _ALWAYS),
     ("saving", "--unregistered_artifacts", dict(action='store_true', default=False,
                                                 help="kept for CLI compatibility (no artefact registry here)"),
      _ALWAYS),

@@ -23,11 +23,15 @@ Operator boundaries mirrored (reference file:line) -- one module per group:
                                                               helper_functions/own_models.py:62-85, attack_PCFA.py:20-37, losses.py
                fgsm_step                                      attack_FGSM.py:21-56,208-209
                pgd_l2_step, pgd_l2_workspace                  (no counterpart: `--step_norm l2`, attack_FGSM.pgd_l2_attack_step)
+  artefacts    flow_maxlen, absmax, flow_to_rgb8, image_to_rgb8
+                                                              flow_library/flow_plot.py:56-105, helper_functions/logging.py:289-339
+                                                              (`--save_png`: packed 8-bit RGB, scales read on the device)
   digest       tensor_digest                                  (no counterpart: the record of pcfa_amd.trace.ClosureTrace)
 """
 from .. import _hip  # noqa: F401
 from ..lbfgs import LBFGS  # noqa: F401  (the attack loop's optimiser: torch.optim.LBFGS semantics, HIP vector math)
 from ..lbfgs import BatchedLBFGS  # noqa: F401  (B of them sharing every closure evaluation: attack_PCFA.PairBatch)
+from .artefacts import *  # noqa: F401,F403
 from .attack_math import *  # noqa: F401,F403
 from .attack_math import _ExtractDeltas  # noqa: F401  (tests / tools reach a few private names through the table)
 from .conv import *  # noqa: F401,F403
