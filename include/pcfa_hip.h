@@ -966,6 +966,33 @@ PCFA_API int pcfa_image_u8(const float* x, const long long strides[4], const flo
                            unsigned char* out, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * Dataset ingest (`--dataset Sintel | Kitti15`): the per-pixel half of reading
+ * a PNG file, the other direction of the picture artefacts.  The host reads the
+ * file and inflates it (helper_functions/png.py); these two launches undo the
+ * scanline filters and unpack the samples into the planar fp32 tensors of
+ * helper_functions/datasets.py (the reference: frame_utils.read_gen /
+ * readFlowKITTI + FlowDataset.__getitem__).  No alignment is asked of the byte
+ * buffers.  Arguments are validated before any launch.  (Added without a change
+ * of PCFA_ABI_VERSION, like the other additive entries.)
+ * ------------------------------------------------------------------------- */
+/* filtered: H scanlines of 1 filter-type byte (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth; the CALLER has checked that none
+ * is larger -- a larger one reconstructs as None) + row_bytes filtered bytes; raw: the H * row_bytes reconstructed bytes
+ * (PNG specification, filter method 0; bpp = bytes per complete pixel).  One workgroup walks a band of at most 1024 rows
+ * as a skewed wavefront (thread = row, one barrier per pixel step, W + rows - 1 steps); taller images are bands launched
+ * one after the other on the stream.  No atomics, nothing shared between launches but `raw`: two calls give equal bytes.
+ * A NULL pointer, H < 1, row_bytes < 1, bpp outside {1, 3, 4, 6} or row_bytes % bpp != 0 is PCFA_ERR_INVALID_ARG. */
+PCFA_API int pcfa_png_unfilter(const unsigned char* filtered, unsigned char* raw, int H, long long row_bytes, int bpp,
+                               void* stream);
+/* raw: [H][W] pixels of kind 0 rgb8 (3 bytes), 1 grey8 (1 byte, tiled to three planes), 2 rgba8 (4 bytes, alpha dropped)
+ * -> out[3][Hp][Wp] fp32 levels in [0, 255]; kind 3 kitti_flow16 (6 bytes: big-endian 16-bit R, G, B) -> out = (u, v, valid)
+ * with u = (R - 32768) / 64, v = (G - 32768) / 64, valid = B, every value exact in fp32.  Hp, Wp: the target of
+ * F.pad(x, (0, Wp - W, 0, Hp - H), "constant", 0), negative differences included: zero outside the source, source beyond
+ * the target cropped.  out: 4-byte aligned; 16-byte stores are used where a piece of four pixels is aligned, with the same
+ * values.  A NULL pointer, a size < 1, a kind outside 0..3 or a misaligned out is PCFA_ERR_INVALID_ARG. */
+PCFA_API int pcfa_samples_to_planar(const unsigned char* raw, int H, int W, int kind, float* out, int Hp, int Wp,
+                                    void* stream);
+
+/* ------------------------------------------------------------------------- *
  * L-BFGS vector math of the attack loop: the memory update and the two-loop
  * recursion inside torch.optim.LBFGS.step (torch==1.7.1 pinned by the reference,
  * scripts/requirements.txt:2; call sites attack_PCFA.py:97,114,382,388 with

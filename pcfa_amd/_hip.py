@@ -223,6 +223,9 @@ SIGNATURES = {
     "pcfa_absmax_items": (c_int, [_P, c_int, c_longlong, _P, _P]),
     "pcfa_flow_colour_u8": (c_int, [_P, _S4, _P, c_int, c_int, c_int, _P, _P]),
     "pcfa_image_u8": (c_int, [_P, _S4, _P, _S4, _P, c_longlong, c_int, c_int, c_int, c_int, _P, _P]),
+    # dataset ingest: inflated PNG scanlines in, reconstructed bytes out; bytes in, planar fp32 [3,Hp,Wp] out
+    "pcfa_png_unfilter": (c_int, [_P, _P, c_int, c_longlong, c_int, _P]),
+    "pcfa_samples_to_planar": (c_int, [_P, c_int, c_int, c_int, _P, c_int, c_int, _P]),
 }
 
 MAX_ITEMS = 16   # PCFA_MAX_ITEMS

@@ -3,7 +3,9 @@
 edited in place, so the same checkout runs from any working directory:
 
     PCFA_WEIGHTS_DIR   where the reference's checkpoint files live (default: models/_pretrained_weights under the cwd)
-    PCFA_SINTEL_DIR / PCFA_KITTI15_DIR   dataset roots (readers are out of scope here, see datasets.py)
+    PCFA_SINTEL_DIR / PCFA_KITTI15_DIR   dataset roots: the directories holding training/ and test/ (Sintel) resp.
+                       training/ and testing/ (KITTI-15), read by datasets.MpiSintel / KITTI; `--dataset_root DIR` on the
+                       command line takes precedence
     PCFA_USE_CPU=1     Conf.config('useCPU') -> True
 """
 import os

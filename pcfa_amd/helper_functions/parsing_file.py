@@ -22,7 +22,12 @@ _FLAGS = [
     ("network", "--weights", dict(default='pretrained', help="NEW: 'pretrained' (checkpoints in "
                                   "$PCFA_WEIGHTS_DIR) or 'random:<seed>'"), _ALWAYS),
     ("dataset", "--dataset", dict(default='Kitti15', choices=['Kitti15', 'Sintel', 'Synthetic'],
-                                  help="image pairs to attack (NEW: 'Synthetic' = seeded pairs, no files)"), _ALWAYS),
+                                  help="image pairs to attack: 'Kitti15' and 'Sintel' are read from --dataset_root (else "
+                                  "$PCFA_KITTI15_DIR / $PCFA_SINTEL_DIR), PNGs decoded on the GPU (NEW: 'Synthetic' = "
+                                  "seeded pairs, no files)"), _ALWAYS),
+    ("dataset", "--dataset_root", dict(default='', metavar='DIR', help="NEW: the directory that holds the dataset's split "
+                                       "folders (Sintel: training/ test/, KITTI-15: training/ testing/); '' = the "
+                                       "environment variable of the dataset"), _ALWAYS),
     ("dataset", "--dataset_stage", dict(default='evaluation', choices=['training', 'evaluation'],
                                         help="dataset split"), _ALWAYS),
     ("dataset", "--small_run", dict(action='store_true', help="debug: first 32 samples only"), _ALWAYS),

@@ -2,7 +2,7 @@
 
 The package ships exactly one implementation, :mod:`pcfa_amd.ops.hip` (HIP
 kernels through the C-ABI; the operators live in the sibling modules corr, conv,
-gru, gma, pwc, flownet, attack_math, artefacts, with core / profiling underneath;
+gru, gma, pwc, flownet, attack_math, artefacts, ingest, with core / profiling underneath;
 ``pcfa_amd.hip_ops`` is an alias of the same module).  It raises on non-GPU tensors and when
 libpcfa_hip.so is missing -- there is no CPU fallback.
 

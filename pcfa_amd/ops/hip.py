@@ -26,7 +26,10 @@ Operator boundaries mirrored (reference file:line) -- one module per group:
   artefacts    flow_maxlen, absmax, flow_to_rgb8, image_to_rgb8
                                                               flow_library/flow_plot.py:56-105, helper_functions/logging.py:289-339
                                                               (`--save_png`: packed 8-bit RGB, scales read on the device)
-  digest       tensor_digest                                  (no counterpart: the record of pcfa_amd.trace.ClosureTrace)
+  ingest       png_unfilter, samples_to_planar                helper_functions/frame_utils.py (read_gen, readFlowKITTI: PIL / OpenCV),
+                                                              datasets.py:66-131 (`--dataset Sintel | Kitti15`: PNG scanline
+                                                              filters undone and samples unpacked, padded, on the device)
+  digest       tensor_digest                                 (no counterpart: the record of pcfa_amd.trace.ClosureTrace)
 """
 from .. import _hip  # noqa: F401
 from ..lbfgs import LBFGS  # noqa: F401  (the attack loop's optimiser: torch.optim.LBFGS semantics, HIP vector math)
@@ -45,6 +48,7 @@ from .flownet import *  # noqa: F401,F403
 from .flownet2 import *  # noqa: F401,F403
 from .gma import *  # noqa: F401,F403
 from .gru import *  # noqa: F401,F403
+from .ingest import *  # noqa: F401,F403
 from .profiling import *  # noqa: F401,F403
 from .pwc import *  # noqa: F401,F403
 from .pwc import _PwcCostVolume  # noqa: F401
